@@ -9,8 +9,8 @@ Workload (config.workload): BASELINE config 3 — Track2D-BlockPartialPZR-v0 (AD
 tat-maze-lstm tracker + target, train-mode -1, 20-step rollouts. A "step" is ONE batched env step of the full
 A3C path: policy forward for both players (PyTorch-ROCm) -> HIP step/observe kernel for all envs (in-launch
 auto-reset) -> every 20th step the n-step/GAE loss, backward, ONE all-reduce of the flat gradient bucket (RCCL)
-and the SharedAdam update. value = (K x envs over all ranks) / max-over-ranks wall time of the MEDIAN of >= 5
-repeats of the K-step region. Two schedules of the same iteration are measured (--schedule both, the default): the
+and the SharedAdam update. value = (K x envs over all ranks) / max-over-ranks wall time of the ONE timed region of
+K = --steps env steps (ms_per_step = that time / K). Two schedules of the same iteration are measured (--schedule both, the default): the
 PIPELINED one (main.py's default: the rollout of iteration i + 1 runs on a second HIP stream while the learner, all-reduce
 and update of iteration i run, every gradient exactly one update late — the bounded form of the reference's worker
 asynchrony; a timed region of K steps = K / 20 phases of that pipeline, each one rollout next to the previous rollout's
@@ -41,6 +41,12 @@ Extra objects on the same JSON line:
   policy_stem  informational f32-MFMA roofline of the conv-stem kernels (the largest single kernels of the iteration).
   cpu_baseline reference-shaped 16-worker (+1 evaluator) CPU A3C on the oracle (oracle/cpu_a3c.py --suite), rank 0, N=1
                only: the headline workload; `cpu_baselines` adds BASELINE config 1 and the env-only 1/16-process rates.
+
+--dump-outputs DIR: after each schedule's headline region (and the pipelined schedule's owed update), rank 0 writes what the
+last timed step computed as DIR/<schedule>_<name>.npy, float32: per env (obs, reward, done, actions, hxs, cxs, eps_len) and
+the last update's loss terms, flat weights and gradient; env_index lists the envs the per-env rows belong to (a fixed seeded
+sample when the whole set would pass 64 MB). The run is seeded and the iteration counts before the region depend on the
+arguments only, so two runs, or two builds, with the same arguments can be compared array for array.
 """
 import argparse
 import json
@@ -65,6 +71,51 @@ sys.path.insert(0, ROOT)
 B_STEP = 1723          # algorithmic bytes per env-step
 B_STEP_U8 = 709        # ... of the u8-observation variant (obs 338 B instead of 1352 B)
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8.0 TB/s spec
+WARMUP_MIN = 200       # env steps before a timed region: measured, a 4096-env region reaches its steady time after ~5 iterations
+DUMP_LIMIT = 64 << 20  # --dump-outputs: bytes over all files (each of the two schedules gets half)
+
+
+def last_step_outputs(player, optimizer, stats, carry=None):
+    """What a caller of the timed iteration holds after its last env step and the update of that rollout, as host arrays:
+    (per_env, flat). per_env (leading dim = envs): the observation the next step acts on, the last step's rewards, done flags
+    and actions, the LSTM state carried into the next rollout, the episode lengths. flat: the four loss terms of the last
+    update, the flat weights after it and the gradient it applied."""
+    c = carry or {}
+    per_env = {"obs": c.get("state", player.state), "reward": getattr(player, "reward", None),
+               "done": c.get("done", player.done), "hxs": c.get("hxs", player.hxs), "cxs": c.get("cxs", player.cxs),
+               "eps_len": c.get("eps_len", player.eps_len)}
+    acts = getattr(player, "_actions_buf", None)               # [T, A, N] store the sampler writes (fused sampling)
+    if acts is not None:
+        per_env["actions"] = acts[-1].t()
+    flat = {k: v for k, v in zip(("policy_loss", "value_loss", "entropy", "pred_loss"), stats or ())}
+    bucket = getattr(optimizer, "bucket", None)
+    if bucket is not None:
+        flat["weights"], flat["grad"] = bucket.flat, bucket.grad
+    else:
+        flat["weights"] = torch.cat([p.detach().reshape(-1) for g in optimizer.param_groups for p in g["params"]])
+
+    def host(t):
+        t = t.detach()
+        return t.cpu().numpy() if t.dtype == torch.float64 else t.float().cpu().numpy()
+    return ({k: host(v) for k, v in per_env.items() if torch.is_tensor(v)},
+            {k: host(v) for k, v in flat.items() if torch.is_tensor(v)})
+
+
+def write_outputs(out_dir, prefix, per_env, flat, limit):
+    """DIR/<prefix>_<name>.npy for every array; when they would pass `limit` bytes, the per-env arrays keep the rows of a fixed
+    seeded sample of envs (the same for every run with the same env count), listed in <prefix>_env_index.npy."""
+    import numpy as np
+    n = min(a.shape[0] for a in per_env.values())
+    per_row = sum(a.nbytes // a.shape[0] for a in per_env.values()) + 8
+    room = limit - sum(a.nbytes for a in flat.values())
+    keep = max(1, min(n, room // per_row))
+    idx = np.arange(n) if keep == n else np.sort(np.random.RandomState(0).choice(n, keep, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = dict(flat, env_index=idx.astype(np.float64), **{k: a[idx] for k, a in per_env.items()})
+    if sum(a.nbytes for a in arrays.values()) > limit:
+        raise SystemExit("bench.py: --dump-outputs: %s outputs do not fit in %d bytes" % (prefix, limit))
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, "%s_%s.npy" % (prefix, k)), a)
 
 
 def _free_port():
@@ -135,8 +186,12 @@ def _lt_status():
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=400)
-    ap.add_argument("--warmup", type=int, default=60)
+    ap.add_argument("--steps", type=int, default=400,
+                    help="env steps in the timed region of each schedule's headline measurement (rounded up to whole 20-step "
+                         "iterations), timed once: ms_per_step = region time / steps")
+    ap.add_argument("--warmup", type=int, default=60,
+                    help="env steps run before each timed region (rounded up to whole 20-step iterations, at least %d: the "
+                         "first iterations after the graphs are captured run up to a tenth slower)" % WARMUP_MIN)
     ap.add_argument("--envs-per-gpu", type=int, default=4096)
     ap.add_argument("--env", default="Track2D-BlockPartialPZR-v0")
     ap.add_argument("--network", default="tat-maze-lstm")
@@ -151,8 +206,11 @@ def main():
                          "fused cell kernel (default: the model's setting)")
     ap.add_argument("--f32-obs", action="store_true", help="float32 observations between env and policy (default: bytes, "
                                                           "decoded in the stem's conv1)")
-    ap.add_argument("--repeats", type=int, default=5, help="minimum number of timed repeats of the K-step region (median "
-                                                          "reported; more are run until they hold >= 1 s of GPU work)")
+    ap.add_argument("--repeats", type=int, default=5, help="shard sweep only: minimum number of timed repeats of its regions "
+                                                          "(median reported; more are run until they hold >= 0.5 s of GPU work)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after each schedule's headline region, write what its last step computed as DIR/<schedule>_<name>.npy "
+                         "(float32; at most %d MB in all)" % (DUMP_LIMIT >> 20))
     ap.add_argument("--schedule", choices=("both", "pipelined", "synchronous"), default="both",
                     help="iteration schedule behind `value`: pipelined (rollout i+1 under learner i, one update of gradient "
                          "delay; train.PipelinedIteration) or synchronous (train.GraphedIteration); both = value from the "
@@ -193,7 +251,7 @@ def main():
     T = 20
     steps = max(T, (a.steps + T - 1) // T * T)          # an A3C iteration is T env steps + one update
     globals_steps = steps
-    warm = max(T, (a.warmup + T - 1) // T * T)
+    warm = max(WARMUP_MIN, (a.warmup + T - 1) // T * T)
     repeats = max(1, a.repeats)
 
     def fence():
@@ -201,10 +259,12 @@ def main():
             dist.barrier()
         torch.cuda.synchronize(device)
 
-    def measure(envs_per_gpu, min_gpu_seconds=1.0, schedule="synchronous", region_steps=None):
-        """Build the player for `envs_per_gpu` envs on this rank, warm up, then time `repeats` repeats of `steps` env
-        steps (region_steps when given), each bracketed by barrier + synchronize; per repeat the MAX over ranks; returns the
-        median repeat."""
+    def measure(envs_per_gpu, min_gpu_seconds=1.0, schedule="synchronous", region_steps=None, dump=None):
+        """Build the player for `envs_per_gpu` envs on this rank and warm up. region_steps None (a headline measurement): time
+        ONE region of exactly `steps` env steps, so that --steps is the number of timed steps and the state the region leaves
+        depends on the arguments alone. region_steps given (the shard sweep): time `repeats` repeats of region_steps steps, more
+        until they hold min_gpu_seconds of GPU work. Each region is bracketed by barrier + synchronize, its time the MAX over
+        ranks; returns the median region. dump: a dict that receives last_step_outputs of the last timed step."""
         steps = globals_steps if region_steps is None else int(region_steps)
         args = default_args(env=a.env, network=a.network, num_envs=envs_per_gpu, num_steps=T, gpu_ids=[local_rank],
                             aux="reward" if "tat" in a.network else "none", train_mode=-1, obs_u8=not a.f32_obs)
@@ -215,18 +275,26 @@ def main():
 
         def eager_iteration():
             rollout(player, T, fast=not a.per_step_autograd)
-            player.optimize(None, optimizer, player.model, args.train_mode, device)
+            return player.optimize(None, optimizer, player.model, args.train_mode, device)
 
         iteration, graphed, drain, trials, flush = eager_iteration, False, (lambda: None), None, (lambda: None)
+        outputs_of = lambda: (player, None)           # (the player whose stores hold the last step, the carried state)
         if schedule == "pipelined":
             sched = PipelinedIteration(player, optimizer, args)
-            trials = [{"ms_per_iteration": round(ms, 4), "chosen": bool(c), "streams": lb} for ms, c, lb in sched.tune_streams()]
+            # the trial length is fixed by the shard size (~50 ms per candidate at the measured iteration times, what the
+            # pilot of tune_streams aims at) rather than timed: how far the trials move the env shard must not depend on the
+            # clock, so that the timed region starts from the same state in every run
+            tune_iters = max(8, min(64, 40960 // envs_per_gpu))
+            trials = [{"ms_per_iteration": round(ms, 4), "chosen": bool(c), "streams": lb}
+                      for ms, c, lb in sched.tune_streams(iters=tune_iters)]
             # timed regions end on a PHASE boundary of the pipeline (sched.sync): each holds K env steps of rollouts and K / T
             # learner updates — the updates of the rollouts one call back
             iteration, graphed, drain, flush = sched.run, True, sched.sync, sched.finish
+            outputs_of = lambda: (sched.players[(sched.i - 1) & 1], sched.carry)
         elif not a.no_graph:
             try:
-                iteration = GraphedIteration(player, optimizer, args, fast=not a.per_step_autograd).run
+                gi = GraphedIteration(player, optimizer, args, fast=not a.per_step_autograd)
+                iteration, outputs_of = gi.run, (lambda: (player, gi.carry))
                 graphed = True
             except Exception as ex:  # fall back to eager, and say so in the JSON line
                 print("hipGraph capture failed, running eagerly: %r" % (ex,), file=sys.stderr)
@@ -235,28 +303,37 @@ def main():
             iteration()
         drain()
 
+        last = [None]
+
         def timed_repeat():
             fence()
             t0 = time.perf_counter()
             for _ in range(steps // T):
-                iteration()
+                last[0] = iteration()
             drain()                      # pipelined: the caller's stream joins both streams; then barrier + synchronize
             fence()
             return time.perf_counter() - t0
-        # whatever --steps is, the timed repeats together hold >= min_gpu_seconds of GPU work (a 20-step region is 6 ms):
-        # a pilot repeat sizes the count, every rank uses the same count (max over ranks of the pilot time)
-        pilot = torch.tensor([timed_repeat()], dtype=torch.float64, device=device)
-        if world > 1:
-            dist.all_reduce(pilot, op=dist.ReduceOp.MAX)
-        reps = max(repeats, int(min_gpu_seconds / max(float(pilot.item()), 1e-6)) + 1)
-        times = [timed_repeat() for _ in range(reps)]
+        if region_steps is None:
+            times = [timed_repeat()]
+        else:
+            # the shard sweep's repeats together hold >= min_gpu_seconds of GPU work (a 20-step region is 6 ms): a pilot
+            # repeat sizes the count, every rank uses the same count (max over ranks of the pilot time)
+            pilot = torch.tensor([timed_repeat()], dtype=torch.float64, device=device)
+            if world > 1:
+                dist.all_reduce(pilot, op=dist.ReduceOp.MAX)
+            reps = max(repeats, int(min_gpu_seconds / max(float(pilot.item()), 1e-6)) + 1)
+            times = [timed_repeat() for _ in range(reps)]
         tt = torch.tensor(times, dtype=torch.float64, device=device)
         if world > 1:
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         ts = sorted(tt.tolist())
         med = ts[len(ts) // 2]
-        flush()
+        reps = len(ts)
+        flush()                          # pipelined: the learner + update of the last rollout (every rollout's gradient applied)
         torch.cuda.synchronize(device)
+        if dump is not None:
+            src, carry = outputs_of()
+            dump["per_env"], dump["flat"] = last_step_outputs(src, optimizer, last[0], carry)
         ar_us = None
         if world > 1:   # the one collective of the path, timed alone: flat fp32 gradient bucket, eager, back to back
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -304,7 +381,10 @@ def main():
                 p_.env.close()
                 del p_, o_
                 torch.cuda.empty_cache()
-        weak, player, optimizer, args = measure(a.envs_per_gpu, schedule=schedule)
+        dump = {} if (a.dump_outputs and rank == 0) else None
+        weak, player, optimizer, args = measure(a.envs_per_gpu, schedule=schedule, dump=dump)
+        if dump:
+            write_outputs(a.dump_outputs, schedule, dump["per_env"], dump["flat"], DUMP_LIMIT // 2)
         if shards is not None:
             shards["sizes"][str(a.envs_per_gpu)] = {k: weak[k] for k in ("value", "ms_per_iteration", "ms_per_step", "repeats",
                                                                          "spread", "stream_trials_ms_per_iteration",
@@ -763,7 +843,10 @@ def main():
             import subprocess
             r = subprocess.run([sys.executable, "-m", "oracle.cpu_a3c", "--suite", "--workers", "16", "--seconds",
                                 str(a.cpu_seconds)], cwd=ROOT, capture_output=True, text=True, timeout=900,
-                               env=dict(os.environ, OMP_NUM_THREADS="1", HIP_VISIBLE_DEVICES=""))
+                               # no GPU in the baseline's processes: the first backward of each worker asks the HIP
+                               # runtime for its devices, which opens the GPU even with HIP_VISIBLE_DEVICES empty;
+                               # GPU_ENABLE_PAL=1 keeps the runtime from bringing up its ROCm device stack at all
+                               env=dict(os.environ, OMP_NUM_THREADS="1", HIP_VISIBLE_DEVICES="", GPU_ENABLE_PAL="1"))
             rows = json.loads(r.stdout.strip().splitlines()[-1])
 
             def entry(cb):

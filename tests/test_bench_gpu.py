@@ -5,15 +5,17 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.mark.gpu
-def test_bench_line_with_the_drivers_flags():
+def test_bench_line_with_the_drivers_flags(tmp_path):
+    out = str(tmp_path / "outputs")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
-                        "--envs-per-gpu", "512", "--global-envs", "1024", "--no-cpu-baseline"],
+                        "--envs-per-gpu", "512", "--global-envs", "1024", "--no-cpu-baseline", "--dump-outputs", out],
                        capture_output=True, text=True, cwd=ROOT, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -24,7 +26,9 @@ def test_bench_line_with_the_drivers_flags():
     assert other in line and "error" not in line[other] and line[other]["value"] > 0
     assert line["value"] >= line[other]["value"]                       # value = the faster schedule's
     assert abs(line["value"] - 20 * 512 / (line["ms_per_step"] * 20 * 1e-3)) / line["value"] < 1e-6
-    assert line["timed_gpu_seconds"] >= 0.5 and line["repeats_run"] >= 5
+    # --steps is the number of timed steps: ONE region of exactly the 20 requested env steps, ms_per_step = its time / 20
+    assert line["repeats_run"] == 1 and line["steps_requested"] == 20
+    assert abs(line["timed_gpu_seconds"] - line["ms_per_step"] * 20 * 1e-3) <= 1e-9 * line["timed_gpu_seconds"]
     sizes = line["shards"]["sizes"]
     assert set(sizes) == {"128", "256", "512"} and all(v["value"] > 0 for v in sizes.values())
     roof = line["roofline"]
@@ -37,6 +41,19 @@ def test_bench_line_with_the_drivers_flags():
     assert roof["policy_state_included"]["bytes_per_env_step"] > 709
     assert "step_f32" in roof["other_variants"] and line["ranks"] == 1
     assert line["config"]["schedule"] == line["schedule"] and "workload" in line["config"]
+    # --dump-outputs: both schedules' last step, float32 (float64 for the env index), 512 envs, at most 64 MB in all
+    names = ("obs", "reward", "done", "actions", "hxs", "cxs", "eps_len", "env_index", "policy_loss", "value_loss",
+             "entropy", "pred_loss", "weights", "grad")
+    want = {"%s_%s.npy" % (s, n) for s in ("synchronous", "pipelined") for n in names}
+    assert set(os.listdir(out)) == want
+    arrays = {f: np.load(os.path.join(out, f)) for f in want}
+    assert sum(x.nbytes for x in arrays.values()) <= 64 << 20
+    for f, x in arrays.items():
+        assert x.dtype in (np.float32, np.float64) and np.isfinite(x).all(), f
+    for s in ("synchronous", "pipelined"):
+        assert np.array_equal(arrays[s + "_env_index.npy"], np.arange(512))
+        assert arrays[s + "_obs.npy"].shape[0] == 512 and arrays[s + "_actions.npy"].shape == (512, 2)
+        assert arrays[s + "_weights.npy"].shape == arrays[s + "_grad.npy"].shape and arrays[s + "_grad.npy"].any()
 
 
 @pytest.mark.gpu
@@ -51,3 +68,22 @@ def test_bench_watchdog_prints_the_synchronous_line_when_the_pipelined_part_does
     assert line["schedule"] == "synchronous" and line["value"] > 0
     assert "did not complete" in line["pipelined"]["error"]
     assert line["roofline"]["in_timed_region"] is True
+
+
+@pytest.mark.gpu
+def test_dumped_outputs_are_the_same_in_every_run_with_the_same_arguments(tmp_path):
+    """--dump-outputs exists so that two builds can be compared output for output: with the same arguments the timed path
+    must start from the same state and compute the same arrays. Two runs, every array bit for bit; --steps 40 times 40 steps."""
+    lines = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "40", "--warmup", "20",
+                            "--envs-per-gpu", "512", "--no-shards", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / run)],
+                           capture_output=True, text=True, cwd=ROOT, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines.append(json.loads(r.stdout.strip().splitlines()[-1]))
+    assert all(x["steps"] == 40 and x["repeats_run"] == 1 for x in lines)
+    files = sorted(os.listdir(str(tmp_path / "a")))
+    assert files == sorted(os.listdir(str(tmp_path / "b"))) and len(files) == 28
+    for f in files:
+        x, y = np.load(str(tmp_path / "a" / f)), np.load(str(tmp_path / "b" / f))
+        assert x.dtype == y.dtype and x.shape == y.shape and np.array_equal(x, y), f

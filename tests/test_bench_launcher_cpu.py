@@ -11,7 +11,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def _env(**kw):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
-    env.update(BENCH_DIST_BACKEND="gloo", BENCH_SINGLE_DEVICE="1", OMP_NUM_THREADS="1", **kw)
+    # GPU_ENABLE_PAL=1: the HIP runtime does not bring up its ROCm device stack, so none of the (up to nine) processes opens
+    # a GPU even where there is one — the check is of the launcher alone
+    env.update(BENCH_DIST_BACKEND="gloo", BENCH_SINGLE_DEVICE="1", OMP_NUM_THREADS="1", GPU_ENABLE_PAL="1", **kw)
     return env
 
 
