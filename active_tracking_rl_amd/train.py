@@ -103,6 +103,21 @@ PREGROW_MODE = os.environ.get("ATR_PREGROW_MODE", "inline")    # pipelined sched
 CORUN_MIN_ENVS = 1024      # PipelinedIteration: the learner's dW kernel in its one-workgroup-per-CU form from this shard size up
 
 
+def captured_learner_ok(num_envs, num_steps):
+    """Whether the learner may be captured in a hipGraph at this shard shape. Refused: more than 512 envs with fewer than
+    4096 rows (T * N) per player — the learner's weight gradients are then computed on the spot instead of in the grouped
+    launch, and in a CAPTURED learner at 1024 envs x 3 steps the tracker-aware target's lstm / fc bias gradients were measured
+    wrong (tests/test_learner_f64_gpu.py) while the same learner run eagerly is right. Such shards run the eager loop."""
+    return not (int(num_envs) > 512 and int(num_envs) * int(num_steps) < 4096)
+
+
+def _refuse_capture(args):
+    if not captured_learner_ok(args.num_envs, args.num_steps):
+        raise RuntimeError("the captured learner is not supported at %d envs x %d steps (more than 512 envs and fewer than 4096 "
+                           "rows per player: train.captured_learner_ok); run the eager loop (--no-graph)"
+                           % (int(args.num_envs), int(args.num_steps)))
+
+
 def clip_flat_grad_(optimizer, max_norm, eps=1e-6):
     """torch.nn.utils.clip_grad_norm_(params, max_norm) (what player_util.py:157 asks for; a no-op in the reference, SURVEY
     quirk 5, hence off unless --max-grad-norm is given) on the flat gradient bucket: the total norm over all parameters is the
@@ -134,6 +149,8 @@ class GraphedIteration(object):
         warm-up iterations and the first captured graph use it. The warm-up iterations are real rollouts + updates run to
         settle allocations before the capture; unless keep_warmup_updates is set their effect on the parameters and the
         optimizer state (step counter, moments) is rolled back, so that iteration 0 of the run is the first replay."""
+        if fast:
+            _refuse_capture(args)
         self.player, self.optimizer, self.args, self.fast = player, optimizer, args, fast
         self.mode0 = args.train_mode if mode is None else int(mode)
         dev = player.device
@@ -360,6 +377,7 @@ class PipelinedIteration(object):
     def __init__(self, player, optimizer, args, warmup=2, mode=None, serial=False):
         from .player_util import Agent
         from .shared_optim import FlatParams
+        _refuse_capture(args)
         self.args, self.optimizer, self.master = args, optimizer, player
         self.mode0 = args.train_mode if mode is None else int(mode)
         self.serial = bool(serial)

@@ -43,7 +43,8 @@ import torch.distributed as dist
 
 from active_tracking_rl_amd import build
 from active_tracking_rl_amd.test import test
-from active_tracking_rl_amd.train import GraphedIteration, PipelinedIteration, make_player, sync_train_modes
+from active_tracking_rl_amd.train import (GraphedIteration, PipelinedIteration, captured_learner_ok, make_player,
+                                          sync_train_modes)
 from active_tracking_rl_amd.utils import ScalarWriter, log_train_scalars
 
 parser = argparse.ArgumentParser(description='A3C (MI355X data-parallel)')
@@ -141,7 +142,11 @@ if __name__ == '__main__':
     first_mode = 0 if args.init_step > 0 else args.train_mode
     train_modes, n_iters = [first_mode] * world, [0] * world
     sched = None
-    if not args.no_graph:
+    use_graph = not args.no_graph and captured_learner_ok(player.num_envs, args.num_steps)
+    if not args.no_graph and not use_graph and rank == 0:
+        print("warning: %d envs x %d steps: the captured learner is not supported at this shape (train.captured_learner_ok); "
+              "running the eager loop" % (player.num_envs, args.num_steps), file=sys.stderr, flush=True)
+    if use_graph:
         if args.schedule == 'pipelined':
             sched = PipelinedIteration(player, optimizer, args, mode=first_mode)
             sched.tune_streams()
