@@ -16,14 +16,20 @@ and update of iteration i run, every gradient exactly one update late — the bo
 asynchrony; a timed region of K steps = K / 20 phases of that pipeline, each one rollout next to the previous rollout's
 update) and the SYNCHRONOUS one (no overlap, no delay). `value` is the faster one's (`schedule` names it), the other's
 numbers ride along in the `synchronous` / `pipelined` object. Weak scaling (`value`): 4096 envs per GPU, independent shards keyed by global env id;
-the strong form of the same metric (4096 envs GLOBAL, 4096/N per GPU — SURVEY §8d's headline) is measured in the same
-run and reported in the `strong` object of the same line.
+with --full, the strong form of the same metric (4096 envs GLOBAL, 4096/N per GPU — SURVEY §8d's headline) is measured in
+the same run and reported in the `strong` object of the same line (at N = 1 the two forms coincide).
+
+A plain run does what the headline needs and nothing else: set up, warm up, time each schedule's region, write
+--dump-outputs, print the line. Everything else it can measure runs only with --full (`"full": true` in the line).
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself (re-exec under
 torch.distributed.run on 127.0.0.1, the role main.py:102-116 plays in the reference); it refuses to report unless
 the process group really has N ranks (checked with an all-reduce of ones and an all-gather of the device ids).
 
-Extra objects on the same JSON line:
+Extra objects on the same JSON line, with --full only:
+  strong       N > 1: the strong form (above; a plain run carries null, N = 1 the weak form's numbers), and `allreduce_us`,
+               the gradient all-reduce timed alone.
+  shards       N = 1: the headline workload at the per-GPU shard sizes of the strong form (4096/8, /4, /2 envs), each schedule.
   roofline     SURVEY 8(d)'s figure for the env kernel OF THE TIMED REGION: algorithmic bytes per env-step (709 B with byte
                observations, 1723 B with float ones) x envs per launch / that kernel's duration IN SITU. Since round 3 the rollout
                ends every env step inside k_act_step (both LSTM cells + heads + draws + env step + observation), so its duration
@@ -39,6 +45,7 @@ Extra objects on the same JSON line:
   env_only     the stand-alone step kernel driven with on-device random actions (no policy): launches/s -> env steps/s, per
                launch and in the persistent mode (t2d_rollout_random: up to 10 steps per launch).
   policy_stem  informational f32-MFMA roofline of the conv-stem kernels (the largest single kernels of the iteration).
+  kernel_sum_per_iteration  rocprofv3's kernel-time total of one replayed iteration, read from the committed profiles/.
   cpu_baseline reference-shaped 16-worker (+1 evaluator) CPU A3C on the oracle (oracle/cpu_a3c.py --suite), rank 0, N=1
                only: the headline workload; `cpu_baselines` adds BASELINE config 1 and the env-only 1/16-process rates.
 
@@ -195,19 +202,23 @@ def main():
     ap.add_argument("--envs-per-gpu", type=int, default=4096)
     ap.add_argument("--env", default="Track2D-BlockPartialPZR-v0")
     ap.add_argument("--network", default="tat-maze-lstm")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the shard sweep, the kernel figures (roofline, env_only, "
+                         "policy_stem), the strong form and the all-reduce timing of an N>1 run, the CPU baselines")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--no-graph", action="store_true", help="run the iteration eagerly instead of as hipGraphs")
     ap.add_argument("--per-step-autograd", action="store_true",
                     help="reference-shaped learner (autograd graph built during the rollout) instead of the "
                          "actor/learner split with time-batched re-evaluation")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0)
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: seconds of each CPU baseline run")
     ap.add_argument("--actor-step", choices=("mfma", "gemm"), default=None,
                     help="A/B switch of the actor's LSTM step: one MFMA kernel (csrc/actor_step_hip.hip) or library GEMMs + "
                          "fused cell kernel (default: the model's setting)")
     ap.add_argument("--f32-obs", action="store_true", help="float32 observations between env and policy (default: bytes, "
                                                           "decoded in the stem's conv1)")
-    ap.add_argument("--repeats", type=int, default=5, help="shard sweep only: minimum number of timed repeats of its regions "
-                                                          "(median reported; more are run until they hold >= 0.5 s of GPU work)")
+    ap.add_argument("--repeats", type=int, default=5, help="--full, shard sweep only: minimum number of timed repeats of its "
+                                                          "regions (median reported; more are run until they hold >= 0.5 s of "
+                                                          "GPU work)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after each schedule's headline region, write what its last step computed as DIR/<schedule>_<name>.npy "
                          "(float32; at most %d MB in all)" % (DUMP_LIMIT >> 20))
@@ -218,8 +229,8 @@ def main():
     ap.add_argument("--pipelined-timeout", type=float, default=240.0,
                     help="seconds the pipelined measurements may take before the line is printed with the synchronous "
                          "numbers only (a watchdog: an N>1 run must not hang the driver)")
-    ap.add_argument("--no-shards", action="store_true", help="skip the per-shard-size sweep of the N=1 line")
-    ap.add_argument("--global-envs", type=int, default=4096, help="env count of the strong-scaling form")
+    ap.add_argument("--no-shards", action="store_true", help="--full without the per-shard-size sweep of the N=1 line")
+    ap.add_argument("--global-envs", type=int, default=4096, help="--full: env count of the strong-scaling form")
     ap.add_argument("--launch-check", action="store_true",
                     help="only start the ranks, verify the communicator and print a stub line (runs without a GPU "
                          "with BENCH_DIST_BACKEND=gloo; covers the launcher in the CPU test-suite)")
@@ -335,7 +346,7 @@ def main():
             src, carry = outputs_of()
             dump["per_env"], dump["flat"] = last_step_outputs(src, optimizer, last[0], carry)
         ar_us = None
-        if world > 1:   # the one collective of the path, timed alone: flat fp32 gradient bucket, eager, back to back
+        if world > 1 and a.full:   # the one collective of the path, timed alone: flat fp32 gradient bucket, eager, back to back
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             for _ in range(5):
                 player.allreduce_grads(optimizer)
@@ -357,10 +368,10 @@ def main():
         return res, player, optimizer, args
 
     def measure_set(schedule, keep_player):
-        """All the timed regions of one schedule: the strong form (N > 1: 4096 envs GLOBAL, sharded), at N = 1 the per-GPU
-        shard sizes of the strong form at every N (4096/8, /4, /2 envs on this one GPU), and the weak form (headline)."""
+        """All the timed regions of one schedule: the weak form (headline) and, with --full, the strong form (N > 1: 4096 envs
+        GLOBAL, sharded) or at N = 1 the per-GPU shard sizes of the strong form at every N (4096/8, /4, /2 envs on this GPU)."""
         strong = None
-        if world > 1:
+        if world > 1 and a.full:
             per = a.global_envs // world
             strong, p_, o_, _ = measure(per, schedule=schedule)
             strong["scaling"] = "strong"
@@ -368,7 +379,7 @@ def main():
             del p_, o_
             torch.cuda.empty_cache()
         shards = None
-        if world == 1 and not a.no_shards:
+        if world == 1 and a.full and not a.no_shards:
             shards = {"note": "headline workload at the per-GPU shard sizes of the strong form (4096 envs over 8/4/2/1 "
                               "GPUs), measured on ONE GPU; the N-GPU strong value is bounded by N x shard value, minus the "
                               "gradient all-reduce (allreduce_us of an N>1 line: %d fp32 elements)" % 0, "sizes": {}}
@@ -391,7 +402,7 @@ def main():
                                                                          "region_steps")}
             shards["note"] = shards["note"].replace("(allreduce_us of an N>1 line: 0 fp32 elements)",
                                                     "(allreduce_us of an N>1 line: %s fp32 elements)" % weak["allreduce_elems"])
-        if strong is None:
+        if strong is None and world == 1:
             strong = dict(weak, scaling="strong", note="N=1: the strong and weak forms coincide")
         if not keep_player:
             player.env.close()
@@ -399,15 +410,142 @@ def main():
             torch.cuda.empty_cache()
         return {"strong": strong, "shards": shards, "weak": weak}, player, optimizer, args
 
-    # the synchronous schedule first (its player also serves the kernel sections below); the pipelined one is measured after
-    # the line is assembled, under a watchdog
+    # the synchronous schedule first (with --full its player also serves the kernel figures); the pipelined one is measured
+    # after the line is assembled, under a watchdog
     first = "pipelined" if (a.schedule == "pipelined" and not a.no_graph) else "synchronous"
     want_pipelined = a.schedule == "both" and not a.no_graph and not a.per_step_autograd
     res0, player, optimizer, args = measure_set(first, keep_player=True)
     strong, shards, weak = res0["strong"], res0["shards"], res0["weak"]
     graphed = weak["hipgraph"]
-    value, n_total = weak["value"], a.envs_per_gpu * world
+    value, n, n_total = weak["value"], a.envs_per_gpu, a.envs_per_gpu * world
+    figures = kernel_figures(a, world, device, player, args, T) if a.full else {}
 
+    line = {
+        "metric": "env steps/sec, Track2D-BlockPartialPZR-v0 @4096 envs, 1/2/4/8 GPU",
+        "value": value, "unit": "env steps/s", "n_gpus": world, "steps": steps, "warmup": a.warmup,
+        "warmup_effective": warm, "steps_requested": a.steps, "repeats": repeats, "spread": weak["spread"],
+        "ms_per_step": weak["ms_per_step"], "ms_per_iteration": weak["ms_per_iteration"],
+        "timed_gpu_seconds": weak["timed_gpu_seconds"], "repeats_run": weak["repeats"], "full": a.full,
+        "shards": shards, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "ranks": comm["ranks"], "rccl_ranks": comm["ranks"] if (comm["backend"] == "nccl" or world == 1) else None,
+        "devices": comm["devices"], "dist_backend": comm["backend"],
+        "allreduce": {"mode": "captured in the update graph" if capture_allreduce_default() else
+                              "eager, between the learner's graph and the update graph",
+                      "hw_queues": os.environ.get("GPU_MAX_HW_QUEUES", "runtime default"),
+                      "basis": "profiles/r04_multirank_1gpu.txt (1-rank RCCL group, collective forced)"},
+        "allreduce_us": weak["allreduce_us"], "allreduce_elems": weak["allreduce_elems"],
+        "weak": {k: weak[k] for k in ("value", "ms_per_step", "envs_per_gpu", "global_envs", "allreduce_us")},
+        "strong": None if strong is None else {k: strong[k] for k in ("value", "ms_per_step", "envs_per_gpu", "global_envs",
+                                                                      "allreduce_us", "spread") if k in strong},
+        "dtype": "u8 map bits / f64 reward -> f32 obs+reward; policy fp32", "data": "synthetic",
+        "config": {"workload": "%s, %d envs/GPU x %d GPU, %s tracker+target, train-mode -1, 20-step A3C rollouts "
+                               "(policy fwd + HIP env step + loss/backward + grad all-reduce + SharedAdam)"
+                               % (a.env, n, world, a.network),
+                   "global_envs": n_total, "rollout": T, "hipgraph": graphed,
+                   "episode_source": "device Philox generators (the reference's sequential algorithms on a counter-based bit source: "
+                                     "bit-exact against the oracle's PHILOX mode, distribution-exact against the reference); the "
+                                     "reference's own numpy-stream episodes also run on the device, draw for draw, for every target "
+                                     "mode (t2d_np_attach: a parity mode, not the timed path)",
+                   "obs": "u8 (t2d_step_u8 -> atr_stem_*_u8)" if getattr(player.env, "obs_u8", False) else "f32",
+                   "gemm_algos": {"torch": "TunableOp picks from tunableop_gfx950.csv" if tuned else "library default",
+                                  "hipblaslt_direct": _lt_status()}, "parallelism": "dp%d (env shards, 1 grad all-reduce/update)" % world},
+    }
+    line.update(figures)
+    sched_note = {"synchronous": "rollout, learner, all-reduce, update in sequence (train.GraphedIteration): every gradient "
+                                 "applied to the weights it was computed on",
+                  "pipelined": "rollout i+1 on a second HIP stream while learner + all-reduce + update i run "
+                               "(train.PipelinedIteration; main.py's default): the same kernels and the same work per "
+                               "iteration, every gradient applied exactly one update late — the bounded form of the "
+                               "reference's Hogwild worker asynchrony (main.py:86-116, train.py:71-95). From 1024 envs "
+                               "per GPU up the learner's grouped weight-gradient GEMM is captured in its co-run form (one "
+                               "workgroup per CU: slower alone, but the other replica's rollout keeps moving beside it)"}
+    line["schedule"] = first
+    line["schedule_note"] = sched_note[first]
+    line["config"]["schedule"] = first
+    if want_pipelined:
+        # a watchdog around the second schedule: if it does not come back (an N>1 run must never hang the driver), rank 0
+        # prints the line as assembled so far — the synchronous numbers — and every rank leaves
+        import threading
+
+        def give_up():
+            if rank == 0:
+                line["pipelined"] = {"error": "the pipelined measurements did not complete within %.0f s; value is the "
+                                              "synchronous schedule's" % a.pipelined_timeout}
+                print(json.dumps(line), flush=True)
+            os._exit(0)
+        dog = threading.Timer(a.pipelined_timeout, give_up)
+        dog.daemon = True
+        dog.start()
+        try:
+            res1, _, _, _ = measure_set("pipelined", keep_player=False)
+            dog.cancel()
+            w1 = res1["weak"]
+            if w1["value"] < weak["value"]:      # the line's value is the faster schedule's; the other one rides along
+                line["pipelined"] = {"value": w1["value"], "ms_per_step": w1["ms_per_step"],
+                                     "ms_per_iteration": w1["ms_per_iteration"], "spread": w1["spread"],
+                                     "shards": res1["shards"], "strong": res1["strong"], "note": sched_note["pipelined"],
+                                     "stream_trials_ms_per_iteration": w1["stream_trials_ms_per_iteration"]}
+                raise StopIteration
+            line["synchronous"] = {"value": weak["value"], "ms_per_step": weak["ms_per_step"],
+                                   "ms_per_iteration": weak["ms_per_iteration"], "spread": weak["spread"],
+                                   "timed_gpu_seconds": weak["timed_gpu_seconds"], "repeats_run": weak["repeats"],
+                                   "allreduce_us": weak["allreduce_us"], "shards": shards, "weak": line["weak"],
+                                   "strong": line["strong"], "note": sched_note["synchronous"]}
+            line.update(value=w1["value"], spread=w1["spread"], ms_per_step=w1["ms_per_step"],
+                        ms_per_iteration=w1["ms_per_iteration"], timed_gpu_seconds=w1["timed_gpu_seconds"],
+                        repeats_run=w1["repeats"], shards=res1["shards"], allreduce_us=w1["allreduce_us"],
+                        stream_trials_ms_per_iteration=w1["stream_trials_ms_per_iteration"],
+                        weak={k: w1[k] for k in ("value", "ms_per_step", "envs_per_gpu", "global_envs", "allreduce_us")},
+                        strong=None if res1["strong"] is None else {
+                            k: res1["strong"][k] for k in ("value", "ms_per_step", "envs_per_gpu", "global_envs", "allreduce_us",
+                                                           "spread") if k in res1["strong"]},
+                        schedule="pipelined", schedule_note=sched_note["pipelined"])
+            line["config"]["schedule"] = "pipelined"
+        except StopIteration:
+            pass
+        except Exception as ex:
+            dog.cancel()
+            line["pipelined"] = {"error": repr(ex)}
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
+        try:
+            # separate process: the baseline forks Hogwild workers, which must not inherit autograd/HIP state.
+            # --suite = BASELINE.md section 3: the headline config and config 1 (BlockPartialRam, maze-lstm, --aux none,
+            # train-mode 0), each 16 workers + 1 evaluator pinned one per physical core, + the env alone on 1 / 16 procs
+            import subprocess
+            r = subprocess.run([sys.executable, "-m", "oracle.cpu_a3c", "--suite", "--workers", "16", "--seconds",
+                                str(a.cpu_seconds)], cwd=ROOT, capture_output=True, text=True, timeout=900,
+                               # no GPU in the baseline's processes: the first backward of each worker asks the HIP
+                               # runtime for its devices, which opens the GPU even with HIP_VISIBLE_DEVICES empty;
+                               # GPU_ENABLE_PAL=1 keeps the runtime from bringing up its ROCm device stack at all
+                               env=dict(os.environ, OMP_NUM_THREADS="1", HIP_VISIBLE_DEVICES="", GPU_ENABLE_PAL="1"))
+            rows = json.loads(r.stdout.strip().splitlines()[-1])
+
+            def entry(cb):
+                return {"value": cb["value"], "unit": "env steps/s", "cores": cb["cores"], "kind": "port",
+                        "config": cb["config"], "cpu_model": cb["cpu_model"], "physical_cores": cb["physical_cores"],
+                        "logical_cpus": cb["host_cpus"], "evaluator_cores": cb["evaluator_cores"], "pinning": cb["pinning"],
+                        "env_only_1proc": cb["env_only_1proc"], "env_only_16proc": cb["env_only_16proc"],
+                        "sample": "%d Hogwild workers + %d evaluator x %.0f s of reference-shaped A3C (%s, %s, --aux %s, "
+                                  "train-mode %d; 1 oracle env + batch-1 policy on torch-CPU per worker, <=20-step "
+                                  "rollouts, SharedAdam); env alone (random actions): %.0f steps/s on 1 process, %.0f on 16"
+                                  % (cb["cores"], cb["evaluator_cores"], cb["seconds"], cb["env"], cb["network"], cb["aux"],
+                                     cb["train_mode"], cb["env_only_1proc"], cb["env_only_16proc"])}
+            line["cpu_baseline"] = entry(rows[0])              # the headline workload's CPU form
+            line["cpu_baselines"] = [entry(cb) for cb in rows]  # + BASELINE config 1
+        except Exception as ex:  # the GPU numbers must still be printed
+            line["cpu_baseline"] = {"value": None, "error": repr(ex)}
+    if rank == 0:
+        print(json.dumps(line))
+    if world > 1:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def kernel_figures(a, world, device, player, args, T):
+    """--full only: the figures of single kernels of the iteration, each from runs of its own on the synchronous
+    schedule's player after its headline region (`roofline`, `env_only`, `policy_stem`), and the committed rocprofv3
+    figures they are read beside (`kernel_sum_per_iteration`). Returns those entries of the JSON line."""
+    from active_tracking_rl_amd.train import rollout
     # ---- roofline of the step/observe kernel: HIP events on the launch stream --------------------------
     # M policy-shaped launches (int64 action tensors, fresh per launch) are captured once into a hipGraph and
     # replayed, so the events bracket back-to-back GPU work rather than the Python/ctypes launch rate. The time
@@ -742,35 +880,8 @@ def main():
     roofline = dict(variants[pick])
     roofline.update(bound="hbm", variant=pick, note=note_k,
                     other_variants={k: v for k, v in variants.items() if k != pick and v is not None})
-    line = {
-        "metric": "env steps/sec, Track2D-BlockPartialPZR-v0 @4096 envs, 1/2/4/8 GPU",
-        "value": value, "unit": "env steps/s", "n_gpus": world, "steps": steps, "warmup": a.warmup,
-        "warmup_effective": warm, "steps_requested": a.steps, "repeats": repeats, "spread": weak["spread"],
-        "ms_per_step": weak["ms_per_step"], "ms_per_iteration": weak["ms_per_iteration"],
-        "timed_gpu_seconds": weak["timed_gpu_seconds"], "repeats_run": weak["repeats"], "kernel_sum_per_iteration": kernel_sum,
-        "shards": shards, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "ranks": comm["ranks"], "rccl_ranks": comm["ranks"] if (comm["backend"] == "nccl" or world == 1) else None,
-        "devices": comm["devices"], "dist_backend": comm["backend"],
-        "allreduce": {"mode": "captured in the update graph" if capture_allreduce_default() else
-                              "eager, between the learner's graph and the update graph",
-                      "hw_queues": os.environ.get("GPU_MAX_HW_QUEUES", "runtime default"),
-                      "basis": "profiles/r04_multirank_1gpu.txt (1-rank RCCL group, collective forced)"},
-        "allreduce_us": weak["allreduce_us"], "allreduce_elems": weak["allreduce_elems"],
-        "weak": {k: weak[k] for k in ("value", "ms_per_step", "envs_per_gpu", "global_envs", "allreduce_us")},
-        "strong": {k: strong[k] for k in ("value", "ms_per_step", "envs_per_gpu", "global_envs", "allreduce_us",
-                                          "spread") if k in strong},
-        "dtype": "u8 map bits / f64 reward -> f32 obs+reward; policy fp32", "data": "synthetic",
-        "config": {"workload": "%s, %d envs/GPU x %d GPU, %s tracker+target, train-mode -1, 20-step A3C rollouts "
-                               "(policy fwd + HIP env step + loss/backward + grad all-reduce + SharedAdam)"
-                               % (a.env, n, world, a.network),
-                   "global_envs": n_total, "rollout": T, "hipgraph": graphed,
-                   "episode_source": "device Philox generators (the reference's sequential algorithms on a counter-based bit source: "
-                                     "bit-exact against the oracle's PHILOX mode, distribution-exact against the reference); the "
-                                     "reference's own numpy-stream episodes also run on the device, draw for draw, for every target "
-                                     "mode (t2d_np_attach: a parity mode, not the timed path)",
-                   "obs": "u8 (t2d_step_u8 -> atr_stem_*_u8)" if getattr(player.env, "obs_u8", False) else "f32",
-                   "gemm_algos": {"torch": "TunableOp picks from tunableop_gfx950.csv" if tuned else "library default",
-                                  "hipblaslt_direct": _lt_status()}, "parallelism": "dp%d (env shards, 1 grad all-reduce/update)" % world},
+    return {
+        "kernel_sum_per_iteration": kernel_sum,
         "roofline": roofline,
         "env_only": {"value": n * world / (eo_us * 1e-6), "unit": "env steps/s", "us_per_launch": eo_us,
                      "note": "same kernel, on-device random actions, one launch per batched step, per-rank x ranks",
@@ -781,93 +892,6 @@ def main():
                                    "per-step launches" % T},
         "policy_stem": stem_roof,
     }
-    sched_note = {"synchronous": "rollout, learner, all-reduce, update in sequence (train.GraphedIteration): every gradient "
-                                 "applied to the weights it was computed on",
-                  "pipelined": "rollout i+1 on a second HIP stream while learner + all-reduce + update i run "
-                               "(train.PipelinedIteration; main.py's default): the same kernels and the same work per "
-                               "iteration, every gradient applied exactly one update late — the bounded form of the "
-                               "reference's Hogwild worker asynchrony (main.py:86-116, train.py:71-95). From 1024 envs "
-                               "per GPU up the learner's grouped weight-gradient GEMM is captured in its co-run form (one "
-                               "workgroup per CU: slower alone, but the other replica's rollout keeps moving beside it)"}
-    line["schedule"] = first
-    line["schedule_note"] = sched_note[first]
-    line["config"]["schedule"] = first
-    if want_pipelined:
-        # a watchdog around the second schedule: if it does not come back (an N>1 run must never hang the driver), rank 0
-        # prints the line as assembled so far — the synchronous numbers — and every rank leaves
-        import threading
-
-        def give_up():
-            if rank == 0:
-                line["pipelined"] = {"error": "the pipelined measurements did not complete within %.0f s; value is the "
-                                              "synchronous schedule's" % a.pipelined_timeout}
-                print(json.dumps(line), flush=True)
-            os._exit(0)
-        dog = threading.Timer(a.pipelined_timeout, give_up)
-        dog.daemon = True
-        dog.start()
-        try:
-            res1, _, _, _ = measure_set("pipelined", keep_player=False)
-            dog.cancel()
-            w1 = res1["weak"]
-            if w1["value"] < weak["value"]:      # the line's value is the faster schedule's; the other one rides along
-                line["pipelined"] = {"value": w1["value"], "ms_per_step": w1["ms_per_step"],
-                                     "ms_per_iteration": w1["ms_per_iteration"], "spread": w1["spread"],
-                                     "shards": res1["shards"], "strong": res1["strong"], "note": sched_note["pipelined"],
-                                     "stream_trials_ms_per_iteration": w1["stream_trials_ms_per_iteration"]}
-                raise StopIteration
-            line["synchronous"] = {"value": weak["value"], "ms_per_step": weak["ms_per_step"],
-                                   "ms_per_iteration": weak["ms_per_iteration"], "spread": weak["spread"],
-                                   "timed_gpu_seconds": weak["timed_gpu_seconds"], "repeats_run": weak["repeats"],
-                                   "allreduce_us": weak["allreduce_us"], "shards": shards, "weak": line["weak"],
-                                   "strong": line["strong"], "note": sched_note["synchronous"]}
-            line.update(value=w1["value"], spread=w1["spread"], ms_per_step=w1["ms_per_step"],
-                        ms_per_iteration=w1["ms_per_iteration"], timed_gpu_seconds=w1["timed_gpu_seconds"],
-                        repeats_run=w1["repeats"], shards=res1["shards"], allreduce_us=w1["allreduce_us"],
-                        stream_trials_ms_per_iteration=w1["stream_trials_ms_per_iteration"],
-                        weak={k: w1[k] for k in ("value", "ms_per_step", "envs_per_gpu", "global_envs", "allreduce_us")},
-                        strong={k: res1["strong"][k] for k in ("value", "ms_per_step", "envs_per_gpu", "global_envs",
-                                                               "allreduce_us", "spread") if k in res1["strong"]},
-                        schedule="pipelined", schedule_note=sched_note["pipelined"])
-            line["config"]["schedule"] = "pipelined"
-        except StopIteration:
-            pass
-        except Exception as ex:
-            dog.cancel()
-            line["pipelined"] = {"error": repr(ex)}
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
-        try:
-            # separate process: the baseline forks Hogwild workers, which must not inherit autograd/HIP state.
-            # --suite = BASELINE.md section 3: the headline config and config 1 (BlockPartialRam, maze-lstm, --aux none,
-            # train-mode 0), each 16 workers + 1 evaluator pinned one per physical core, + the env alone on 1 / 16 procs
-            import subprocess
-            r = subprocess.run([sys.executable, "-m", "oracle.cpu_a3c", "--suite", "--workers", "16", "--seconds",
-                                str(a.cpu_seconds)], cwd=ROOT, capture_output=True, text=True, timeout=900,
-                               # no GPU in the baseline's processes: the first backward of each worker asks the HIP
-                               # runtime for its devices, which opens the GPU even with HIP_VISIBLE_DEVICES empty;
-                               # GPU_ENABLE_PAL=1 keeps the runtime from bringing up its ROCm device stack at all
-                               env=dict(os.environ, OMP_NUM_THREADS="1", HIP_VISIBLE_DEVICES="", GPU_ENABLE_PAL="1"))
-            rows = json.loads(r.stdout.strip().splitlines()[-1])
-
-            def entry(cb):
-                return {"value": cb["value"], "unit": "env steps/s", "cores": cb["cores"], "kind": "port",
-                        "config": cb["config"], "cpu_model": cb["cpu_model"], "physical_cores": cb["physical_cores"],
-                        "logical_cpus": cb["host_cpus"], "evaluator_cores": cb["evaluator_cores"], "pinning": cb["pinning"],
-                        "env_only_1proc": cb["env_only_1proc"], "env_only_16proc": cb["env_only_16proc"],
-                        "sample": "%d Hogwild workers + %d evaluator x %.0f s of reference-shaped A3C (%s, %s, --aux %s, "
-                                  "train-mode %d; 1 oracle env + batch-1 policy on torch-CPU per worker, <=20-step "
-                                  "rollouts, SharedAdam); env alone (random actions): %.0f steps/s on 1 process, %.0f on 16"
-                                  % (cb["cores"], cb["evaluator_cores"], cb["seconds"], cb["env"], cb["network"], cb["aux"],
-                                     cb["train_mode"], cb["env_only_1proc"], cb["env_only_16proc"])}
-            line["cpu_baseline"] = entry(rows[0])              # the headline workload's CPU form
-            line["cpu_baselines"] = [entry(cb) for cb in rows]  # + BASELINE config 1
-        except Exception as ex:  # the GPU numbers must still be printed
-            line["cpu_baseline"] = {"value": None, "error": repr(ex)}
-    if rank == 0:
-        print(json.dumps(line))
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

@@ -1,5 +1,6 @@
-"""bench.py end to end on the GPU with the driver's own flags (small shard, no CPU baseline): the JSON line carries both
-schedules, the shards, the roofline of the timed region's env kernel — and the run comes back."""
+"""bench.py end to end on the GPU. With --full (small shard, no CPU baseline) the JSON line carries both schedules, the
+shards, the roofline of the timed region's env kernel — and the run comes back. A plain run (the driver's flags) measures
+the headline alone and computes what the --full run computes."""
 import json
 import os
 import subprocess
@@ -15,12 +16,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_line_with_the_drivers_flags(tmp_path):
     out = str(tmp_path / "outputs")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
-                        "--envs-per-gpu", "512", "--global-envs", "1024", "--no-cpu-baseline", "--dump-outputs", out],
+                        "--envs-per-gpu", "512", "--global-envs", "1024", "--full", "--no-cpu-baseline", "--dump-outputs", out],
                        capture_output=True, text=True, cwd=ROOT, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["metric"].startswith("env steps/sec") and line["unit"] == "env steps/s" and line["n_gpus"] == 1
-    assert line["steps"] == 20 and line["higher_is_better"] is True and line["scaling"] == "weak"
+    assert line["steps"] == 20 and line["higher_is_better"] is True and line["scaling"] == "weak" and line["full"] is True
     assert line["schedule"] in ("pipelined", "synchronous")
     other = "synchronous" if line["schedule"] == "pipelined" else "pipelined"
     assert other in line and "error" not in line[other] and line[other]["value"] > 0
@@ -61,7 +62,7 @@ def test_bench_watchdog_prints_the_synchronous_line_when_the_pipelined_part_does
     """--pipelined-timeout far below what the pipelined measurements need: the watchdog fires, rank 0 prints the line as
     assembled so far (the synchronous numbers) and the process leaves with exit code 0 — an N>1 run must never hang the driver."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
-                        "--envs-per-gpu", "512", "--no-shards", "--no-cpu-baseline", "--pipelined-timeout", "0.01"],
+                        "--envs-per-gpu", "512", "--full", "--no-shards", "--no-cpu-baseline", "--pipelined-timeout", "0.01"],
                        capture_output=True, text=True, cwd=ROOT, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -86,4 +87,35 @@ def test_dumped_outputs_are_the_same_in_every_run_with_the_same_arguments(tmp_pa
     assert files == sorted(os.listdir(str(tmp_path / "b"))) and len(files) == 28
     for f in files:
         x, y = np.load(str(tmp_path / "a" / f)), np.load(str(tmp_path / "b" / f))
+        assert x.dtype == y.dtype and x.shape == y.shape and np.array_equal(x, y), f
+
+
+@pytest.mark.gpu
+def test_a_plain_run_measures_the_headline_alone_and_computes_what_a_full_run_computes(tmp_path):
+    """Without --full the run sets up, warms up, times both schedules' regions, dumps and prints: no shard sweep, no kernel
+    figures, no CPU baseline. What moved behind --full runs outside the headline regions, so the two runs' last timed steps
+    must agree array for array."""
+    lines = {}
+    for run, extra in (("plain", []), ("full", ["--full", "--global-envs", "1024", "--no-cpu-baseline"])):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
+                            "--envs-per-gpu", "512", "--dump-outputs", str(tmp_path / run)] + extra,
+                           capture_output=True, text=True, cwd=ROOT, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines[run] = json.loads(r.stdout.strip().splitlines()[-1])
+    line = lines["plain"]
+    assert line["full"] is False and line["steps"] == 20 and line["repeats_run"] == 1 and line["value"] > 0
+    assert line["metric"] == lines["full"]["metric"] and line["unit"] == "env steps/s" and line["higher_is_better"] is True
+    assert line["dtype"] == lines["full"]["dtype"]
+    assert abs(line["value"] - 20 * 512 / (line["ms_per_step"] * 20 * 1e-3)) / line["value"] < 1e-6
+    other = "synchronous" if line["schedule"] == "pipelined" else "pipelined"
+    assert "error" not in line[other] and 0 < line[other]["value"] <= line["value"]
+    assert line["shards"] is None and line[other]["shards"] is None
+    for key in ("roofline", "env_only", "policy_stem", "kernel_sum_per_iteration", "cpu_baseline", "cpu_baselines"):
+        assert key not in line, key
+    assert lines["full"]["full"] is True and set(lines["full"]["shards"]["sizes"]) == {"128", "256", "512"}
+    assert "roofline" in lines["full"] and "env_only" in lines["full"] and "policy_stem" in lines["full"]
+    files = sorted(os.listdir(str(tmp_path / "plain")))
+    assert files == sorted(os.listdir(str(tmp_path / "full"))) and len(files) == 28
+    for f in files:
+        x, y = np.load(str(tmp_path / "plain" / f)), np.load(str(tmp_path / "full" / f))
         assert x.dtype == y.dtype and x.shape == y.shape and np.array_equal(x, y), f

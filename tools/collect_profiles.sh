@@ -5,10 +5,10 @@
 TAG=${1:-r02}
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$TAG; mkdir -p $O
 export PYTHONPATH=$R; cd /tmp; export TMPDIR=/tmp
-timeout 900 python $R/bench.py > $O/bench.json 2> $O/bench.err
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_bench -- python $R/bench.py --no-cpu-baseline > $O/bench_under_rocprof.json 2> /dev/null
+timeout 900 python $R/bench.py --full > $O/bench.json 2> $O/bench.err
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_bench -- python $R/bench.py --full --no-cpu-baseline > $O/bench_under_rocprof.json 2> /dev/null
 python $R/tools/summarize_prof.py stats /tmp/p_bench > $O/bench_kernel_stats.txt
-BENCH_SINGLE_DEVICE=1 BENCH_DIST_BACKEND=gloo timeout 900 python $R/bench.py --gpus 2 --steps 100 --warmup 20 > $O/bench_selflaunch_2ranks_gloo_1gpu.json 2> $O/bench_selflaunch_2ranks_gloo_1gpu.err
+BENCH_SINGLE_DEVICE=1 BENCH_DIST_BACKEND=gloo timeout 900 python $R/bench.py --gpus 2 --steps 100 --warmup 20 --full > $O/bench_selflaunch_2ranks_gloo_1gpu.json 2> $O/bench_selflaunch_2ranks_gloo_1gpu.err
 for n in 4096 65536 262144; do
   rm -rf /tmp/p_env; timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_env -- python $R/tools/env_only_bench.py --n $n --steps 1000 > $O/env_only_$n.txt 2> /dev/null
   python $R/tools/summarize_prof.py stats /tmp/p_env > $O/env_only_kernel_stats_$n.txt
