@@ -53,6 +53,11 @@ int atr_stem_backward_u8(const unsigned char *x, long long x_stride, const float
  * uint64 that the call advances by one in stream order when bump != 0, so hipGraph replays draw fresh numbers;
  * `ordinal` distinguishes the calls made between two bumps (e.g. bump once per rollout, ordinal = call index inside
  * it: one tiny launch per rollout instead of one per call). n == 0 with bump != 0 only advances the counter.
+ * The key in full: Philox counter words (row, counter & 0xffffffff, counter >> 32, 0x5A3D0000 ^ ordinal), key words
+ * (seed & 0xffffffff, seed >> 32); u = ((x0 >> 8) + 0.5) / 2^24 of the first output word; action = first a with
+ * u < CDF[a] of softmax(logits), A - 1 if none. A call with bump != 0 draws under the counter value BEFORE its own bump
+ * (the bump is a second launch behind the draw); a block opened by an n == 0 bump draws under the value after it.
+ * tests/draw_spec.py is this specification on the host; tests/test_action_draws_gpu.py holds every draw kernel to it.
  * actions: int64 [n]. */
 int atr_sample_actions(const float *h, const float *w, const float *b, long long *actions, unsigned long long *counter,
                        unsigned long long seed, unsigned ordinal, int bump, int n, int R, int A, void *stream);
@@ -105,7 +110,11 @@ int atr_lstm_cell_forward_act2(const float *ig, const float *hg, const float *bi
  * whole pre-activation); bias[p] [4R] (nullable, added here); c_prev[p] / h_out[p] / c_out[p] [N,R]; acts[p] [N,4R]
  * (nullable: activated gates for atr_lstm_cell_backward); actor_w[p] [A,R], actor_b[p] [A]. done_prev [N] (nullable): the
  * previous step's done flags (k = done == 0 masks hg and c_prev). actions_out int64 [2,N]. Draw key: (seed; row, *counter,
- * ordinal + p) — the key of atr_lstm_cell_forward_act*. R must be 128. */
+ * ordinal + p) — the key of atr_lstm_cell_forward_act*. R must be 128.
+ * Ordinals of a rollout as the drivers issue them (fused.ActionSampler: the block's ordinals start at 1): step t
+ * (0 .. T - 1) passes ordinal = 2t + 1, so the tracker draws under 2t + 1 and the target under 2t + 2; the learner's
+ * bootstrap step reopens the block and continues at 2T + 1 / 2T + 2, under the same counter value — the one the rollout's
+ * first launch left (it bumps before any draw). */
 typedef struct atr_act_step {
     const float *ig[2];
     const float *hg[2];
