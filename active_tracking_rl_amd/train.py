@@ -12,15 +12,18 @@ steps -> optimize -> log), with these MI355X-first substitutions:
   * the rollout is always `num_steps` long — finished envs auto-reset in the step launch (see player_util).
 `train_modes` / `n_iters` may be plain lists (single process) or mp.Manager lists as in main.py:103-105.
 """
+import contextlib
 import os
 import time
 
 import torch
+import torch.distributed as dist
 
+from . import fused
 from .environment import create_env
-from .model import build_model
+from .model import CNN_maze, build_model
 from .player_util import Agent
-from .shared_optim import SharedAdam, make_optimizer  # noqa: F401  (SharedAdam re-exported for callers)
+from .shared_optim import FlatParams, SharedAdam, make_optimizer  # noqa: F401  (SharedAdam re-exported for callers)
 
 
 def default_args(**over):
@@ -130,7 +133,105 @@ def clip_flat_grad_(optimizer, max_norm, eps=1e-6):
     g.mul_(coef)
 
 
-class GraphedIteration(object):
+@contextlib.contextmanager
+def rolled_back(tensors):
+    """Whatever the body writes to `tensors` is undone when it ends: cloned on entry, copied back on exit (None: nothing to
+    undo). The copies go out on the current stream: the body leaves the device work it wants undone ordered before its end."""
+    saved = None if tensors is None else [t.clone() for t in tensors]
+    yield
+    if saved is not None:
+        with torch.no_grad():
+            for t, v in zip(tensors, saved):
+                t.copy_(v)
+
+
+def update_tensors(optimizer, extra=(), grad=False):
+    """Every tensor an update writes, each once: the flat parameter bucket, its gradient if `grad` (written by the learner
+    rather than by the update), the optimizer's own state tensors, then `extra`. None for an optimizer without a flat bucket."""
+    bucket = getattr(optimizer, "bucket", None)
+    if bucket is None:
+        return None
+    seen, out = set(), []
+    for t in [bucket.flat] + ([bucket.grad] if grad else []) \
+            + [v for v in vars(optimizer).values() if isinstance(v, torch.Tensor)] + list(extra):
+        if t.data_ptr() not in seen and t.numel() > 0:
+            seen.add(t.data_ptr())
+            out.append(t)
+    return out
+
+
+class _GraphedSchedule(object):
+    """What the two graphed drivers share: the carry (the tensors every captured rollout starts from and hands on), the update
+    graph, and burn_in. A driver sets master (the player that counts env steps and all-reduces), optimizer, args and
+    capture_allreduce, and says which tensors its updates write (_written)."""
+
+    def finish(self):
+        """Issue whatever the schedule still owes: nothing, unless the driver defers work (PipelinedIteration)."""
+
+    def _new_carry(self):
+        p = self.master
+        self.carry = dict(state=p.state.clone(), hxs=p.hxs.detach().clone(), cxs=p.cxs.detach().clone(),
+                          done=p.done.clone(), eps_len=p.eps_len.clone())
+
+    def _bind_carry(self, p):
+        p.state, p.hxs, p.cxs = self.carry["state"], self.carry["hxs"], self.carry["cxs"]
+        p.done, p.eps_len = self.carry["done"], self.carry["eps_len"]
+
+    @contextlib.contextmanager
+    def _carried(self, p):
+        """Inside a capture, around rollout(p) and whatever is to be captured between it and the carry copies: p starts from the
+        carry, and what the next rollout starts from is in the carry when the block ends."""
+        self._bind_carry(p)
+        p.carry_out, p.carry_written = self.carry, ()             # the rollout's epilogue kernel publishes the carry
+        yield
+        for key, src in (("state", p.state), ("hxs", p.hxs.detach()), ("cxs", p.cxs.detach()), ("done", p.done),
+                         ("eps_len", p.eps_len)):
+            if key in p.carry_written:
+                continue
+            if self.carry[key].data_ptr() != src.data_ptr():      # (the epilogue kernel advances eps_len in place)
+                self.carry[key].copy_(src)
+        p.carry_out = None
+
+    def _capture_update(self, replica=None):
+        """The update graph: [all-reduce,] clip, optimizer step on the master weights [, master weights -> replica's copy]."""
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, capture_error_mode="thread_local"):
+            if self.capture_allreduce:
+                self.master.allreduce_grads(self.optimizer)
+            clip_flat_grad_(self.optimizer, getattr(self.args, "max_grad_norm", None))
+            self.optimizer.step()
+            if replica is not None:
+                replica.flat.copy_(self.optimizer.bucket.flat)
+        return g
+
+    def burn_in(self, iters, mode=None):
+        """`iters` iterations whose updates are DISCARDED (weights, optimizer state and step counter restored): only the env
+        shard moves on. Why a driver wants this: every env of a fresh shard starts an episode at step 0 together, so for the first
+        ~25 rollouts the batch is perfectly correlated in episode phase (all trackers next to their targets, no episode end in
+        any of them), and with 1024+ envs per update the first Adam steps fit that one phase. Measured on
+        Track2D-MazePartialNav-v0 / 1024 envs / train-mode 0 over 8 seeds x 3000 iterations: 3 of 8 runs reach the +0.63
+        plateau from a synchronised start, 6 of 8 after 300 discarded iterations (profiles/r05_learning_seeds_*.txt). The
+        reference's 16 asynchronous one-env workers drift apart on their own (train.py:71-95)."""
+        if iters <= 0:
+            return
+        tensors = self._written()
+        if tensors is None:
+            raise RuntimeError("burn_in needs the flat-bucket optimizer (weights and optimizer state as a few tensors to restore); "
+                               "this optimizer has none: its updates would be KEPT")
+        dev = self.master.device
+        self.finish()
+        torch.cuda.synchronize(dev)
+        n0 = self.master.n_steps
+        with rolled_back(tensors):
+            for _ in range(int(iters)):
+                self.run(mode)
+            self.finish()
+            torch.cuda.synchronize(dev)
+        self.master.n_steps = n0
+        torch.cuda.synchronize(dev)
+
+
+class GraphedIteration(_GraphedSchedule):
     """One A3C iteration (20-step rollout -> loss -> backward | all-reduce | SharedAdam) replayed as two hipGraphs.
 
     The rollout is launch-bound in eager mode (~60 small kernels per env step); capturing it removes the host
@@ -151,55 +252,31 @@ class GraphedIteration(object):
         optimizer state (step counter, moments) is rolled back, so that iteration 0 of the run is the first replay."""
         if fast:
             _refuse_capture(args)
-        self.player, self.optimizer, self.args, self.fast = player, optimizer, args, fast
+        self.player = self.master = player
+        self.optimizer, self.args, self.fast = optimizer, args, fast
         self.mode0 = args.train_mode if mode is None else int(mode)
         dev = player.device
         snap = None if keep_warmup_updates else self._optimizer_tensors()
-        saved = [t.clone() for t in snap] if snap is not None else None
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                self._eager()
-        torch.cuda.current_stream(dev).wait_stream(side)
-        torch.cuda.synchronize(dev)
-        if saved is not None:
-            with torch.no_grad():
-                for t, v in zip(snap, saved):
-                    t.copy_(v)
-        self.carry = dict(state=player.state.clone(), hxs=player.hxs.detach().clone(),
-                          cxs=player.cxs.detach().clone(), done=player.done.clone(), eps_len=player.eps_len.clone())
+        with rolled_back(snap):
+            side = torch.cuda.Stream(device=dev)
+            side.wait_stream(torch.cuda.current_stream(dev))
+            with torch.cuda.stream(side):
+                for _ in range(warmup):
+                    self._eager()
+            torch.cuda.current_stream(dev).wait_stream(side)
+            torch.cuda.synchronize(dev)
+        self._new_carry()
         self.g_rolls, self.stats_by_mode = {}, {}
         self._capture(self.mode0)
         self.capture_allreduce = capture_allreduce_default()
-        self.g_opt = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.g_opt, capture_error_mode="thread_local"):
-            if self.capture_allreduce:
-                player.allreduce_grads(optimizer)
-            clip_flat_grad_(optimizer, getattr(args, "max_grad_norm", None))
-            optimizer.step()
-        if saved is not None:          # (capturing a graph does not execute it; restore anyway in case a backend ran it)
-            with torch.no_grad():
-                for t, v in zip(snap, saved):
-                    t.copy_(v)
+        with rolled_back(snap):        # (capturing a graph does not execute it; restore anyway in case a backend ran it)
+            self.g_opt = self._capture_update()
 
     def _optimizer_tensors(self):
         """Every tensor an update writes: the flat parameter bucket and the optimizer's own state tensors."""
-        opt = self.optimizer
-        bucket = getattr(opt, "bucket", None)
-        if bucket is None:
-            return None
-        seen, out = set(), []
-        for t in [bucket.flat] + [v for v in vars(opt).values() if isinstance(v, torch.Tensor)]:
-            if t.data_ptr() not in seen and t.numel() > 0:
-                seen.add(t.data_ptr())
-                out.append(t)
-        return out
+        return update_tensors(self.optimizer)
 
-    def _bind_carry(self):
-        p = self.player
-        p.state, p.hxs, p.cxs = self.carry["state"], self.carry["hxs"], self.carry["cxs"]
-        p.done, p.eps_len = self.carry["done"], self.carry["eps_len"]
+    _written = _optimizer_tensors
 
     def _capture(self, mode):
         player, args = self.player, self.args
@@ -208,9 +285,7 @@ class GraphedIteration(object):
         torch.cuda.synchronize(player.device)
         g = torch.cuda.CUDAGraph()
         # thread_local: an RCCL watchdog thread polling events must not invalidate the capture
-        with torch.cuda.graph(g, capture_error_mode="thread_local"):
-            self._bind_carry()
-            player.carry_out, player.carry_written = self.carry, ()   # the rollout's epilogue kernel publishes the carry
+        with torch.cuda.graph(g, capture_error_mode="thread_local"), self._carried(player):
             rollout(player, args.num_steps, fast=self.fast)
             # (growing the next passes' Maze maps on a forked stream under the learner — env.pregrow(fork=True) here — was
             # measured: -2 % on configs[3] / [4]: on one stream the growth only moves from the pass to the fork, and the fork /
@@ -220,47 +295,15 @@ class GraphedIteration(object):
             stats = player.compute_grads(self.optimizer, mode)
             if hasattr(player.env, "generator_join"):
                 player.env.generator_join()   # the env's forked generator launches end inside the captured region
-            for k, src in (("state", player.state), ("hxs", player.hxs.detach()), ("cxs", player.cxs.detach()),
-                           ("done", player.done), ("eps_len", player.eps_len)):
-                if k in player.carry_written:
-                    continue
-                if self.carry[k].data_ptr() != src.data_ptr():    # (the epilogue kernel advances eps_len in place)
-                    self.carry[k].copy_(src)
-            player.carry_out = None
-        self._bind_carry()
+            # (the carry copies of _carried come here: after the learner and the join)
+        self._bind_carry(player)
         self.g_rolls[mode], self.stats_by_mode[mode] = g, stats
-        self.g_roll, self.stats = g, stats          # the most recently captured pair (kept for callers/tools)
+        self.stats = stats               # (of the most recently captured graph, until run() sets it)
         return g
 
     def _eager(self):
         rollout(self.player, self.args.num_steps, fast=self.fast)
         self.player.optimize(None, self.optimizer, self.player.model, self.mode0, self.player.device)
-
-    def burn_in(self, iters, mode=None):
-        """`iters` iterations whose updates are DISCARDED (weights, optimizer state and step counter restored): only the env
-        shard moves on. Why a driver wants this: every env of a fresh shard starts an episode at step 0 together, so for the first
-        ~25 rollouts the batch is perfectly correlated in episode phase (all trackers next to their targets, no episode end in
-        any of them), and with 1024+ envs per update the first Adam steps fit that one phase. Measured on
-        Track2D-MazePartialNav-v0 / 1024 envs / train-mode 0 over 8 seeds x 3000 iterations: 3 of 8 runs reach the +0.63
-        plateau from a synchronised start, 6 of 8 after 300 discarded iterations (profiles/r05_learning_seeds_*.txt). The
-        reference's 16 asynchronous one-env workers drift apart on their own (train.py:71-95)."""
-        if iters <= 0:
-            return
-        tensors = self._optimizer_tensors()
-        if tensors is None:
-            raise RuntimeError("burn_in needs the flat-bucket optimizer (weights and optimizer state as a few tensors to restore); "
-                               "this optimizer has none: its updates would be KEPT")
-        saved = [t.clone() for t in tensors]
-        n0 = self.player.n_steps
-        for _ in range(int(iters)):
-            self.run(mode)
-        torch.cuda.synchronize(self.player.device)
-        if saved is not None:
-            with torch.no_grad():
-                for t, v in zip(tensors, saved):
-                    t.copy_(v)
-        self.player.n_steps = n0
-        torch.cuda.synchronize(self.player.device)
 
     def run(self, mode=None):
         mode = self.mode0 if mode is None else int(mode)
@@ -333,7 +376,6 @@ def cu_masked_stream(device, first_cu, n_cus, total_cus=None):
     if rc != 0 or not st.value:
         raise RuntimeError("hipExtStreamCreateWithCUMask failed (%d)" % rc)
     _masked_streams[key] = torch.cuda.ExternalStream(st.value, device=device)
-    from . import fused
     fused.register_stream_cus(_masked_streams[key], n_cus)       # (launches whose workgroups wait for each other size their grid by it)
     return _masked_streams[key]
 
@@ -345,7 +387,7 @@ class _BucketOnly(object):
         self.bucket = bucket
 
 
-class PipelinedIteration(object):
+class PipelinedIteration(_GraphedSchedule):
     """A3C iterations with the rollout of iteration i + 1 running WHILE the learner of iteration i runs: two HIP streams, each
     replaying hipGraphs, events between them — no host synchronisation, no fork / join inside a graph.
 
@@ -375,8 +417,6 @@ class PipelinedIteration(object):
     half of the CUs — by trial."""
 
     def __init__(self, player, optimizer, args, warmup=2, mode=None, serial=False):
-        from .player_util import Agent
-        from .shared_optim import FlatParams
         _refuse_capture(args)
         self.args, self.optimizer, self.master = args, optimizer, player
         self.mode0 = args.train_mode if mode is None else int(mode)
@@ -384,21 +424,17 @@ class PipelinedIteration(object):
         # Whole-map ('Full') observations go through F.conv2d, i.e. MIOpen's kernels: replayed next to another stream's graph
         # they were observed to hang the device (their workgroups wait on each other and need the chip to themselves). Those
         # ids (no BASELINE configuration uses them) run the same schedule in program order on one stream.
-        from .model import CNN_maze
         if any(isinstance(m, CNN_maze) and not m.small for m in player.model.modules()):
             self.serial = True
         dev = self.dev = player.device
         env = player.env
         # eager warm-up on the master (allocator, GEMM workspaces), its updates rolled back
-        tensors = [optimizer.bucket.flat] + [v for v in vars(optimizer).values() if isinstance(v, torch.Tensor)]
-        saved = [t.clone() for t in tensors]
-        for _ in range(warmup):
-            rollout(player, args.num_steps)
-            player.optimize(None, optimizer, player.model, self.mode0, dev)
-        torch.cuda.synchronize(dev)
-        with torch.no_grad():
-            for t, v in zip(tensors, saved):
-                t.copy_(v)
+        tensors = update_tensors(optimizer)
+        with rolled_back(tensors):
+            for _ in range(warmup):
+                rollout(player, args.num_steps)
+                player.optimize(None, optimizer, player.model, self.mode0, dev)
+            torch.cuda.synchronize(dev)
         # the two replicas: same architecture, weights re-homed in flat buffers laid out like the optimizer's bucket
         self.players, self.buckets = [], []
         for k in range(2):
@@ -414,14 +450,12 @@ class PipelinedIteration(object):
             assert bucket.flat.numel() == optimizer.bucket.flat.numel()
             # a draw stream of its own: the learner's bootstrap step reads the replica's counter, which only the replica's
             # own rollouts advance (they wait for this learner), so its draws do not depend on the timing of the other stream
-            from . import fused
             m._sampler = fused.ActionSampler(dev, seed=(int(torch.initial_seed()) + 7919 * (k + 1)) & 0xFFFFFFFFFFFFFFFF)
             a = Agent(m, env, args, None, dev)
             a.w_entropy_target = player.w_entropy_target
             self.players.append(a)
             self.buckets.append(bucket)
-        self.carry = dict(state=player.state.clone(), hxs=player.hxs.detach().clone(), cxs=player.cxs.detach().clone(),
-                          done=player.done.clone(), eps_len=player.eps_len.clone())
+        self._new_carry()
         # (stream priorities were measured and make no difference to the overlap: ATR_PIPE_PRIO=1 / 2 raises the rollout's /
         # the learner's stream for experiments; what matters is which hardware queues and CUs the pair gets — tune_streams)
         prio = int(os.environ.get("ATR_PIPE_PRIO", "0"))
@@ -446,19 +480,9 @@ class PipelinedIteration(object):
         self.capture_allreduce = capture_allreduce_default()
         self.pending = None       # (replica, learner graph) of the rollout whose learner has not been issued yet
         self.graphs = {}          # (mode, k) -> (rollout graph, learner graph, stats)
-        self.g_opt = []
-        for k in range(2):        # O_k: the update on theta, then theta -> F_k
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                if self.capture_allreduce:
-                    player.allreduce_grads(optimizer)
-                clip_flat_grad_(optimizer, getattr(args, "max_grad_norm", None))
-                optimizer.step()
-                self.buckets[k].flat.copy_(optimizer.bucket.flat)
-            self.g_opt.append(g)
+        with rolled_back(tensors):     # (capturing a graph does not execute it; restore anyway in case a backend ran it)
+            self.g_opt = [self._capture_update(b) for b in self.buckets]        # O_k: the update on theta, then theta -> F_k
         with torch.no_grad():
-            for t, v in zip(tensors, saved):
-                t.copy_(v)
             for b in self.buckets:
                 b.flat.copy_(optimizer.bucket.flat)
         self.i = 0
@@ -477,7 +501,6 @@ class PipelinedIteration(object):
         step's last workgroups are waiting for (measured: barrier time-outs). So: on a masked rollout stream the replicas are
         told its CU count (a rollout graph captured for the whole chip must not be replayed on half of it), on a shared pair
         they keep the four-launch step. Returns True when the setting changed (graphs captured earlier are then stale)."""
-        from . import fused
         masked = int(self.sR.cuda_stream) in fused._stream_cus
         wg = fused.stream_cus(self.dev, self.sR) if (masked or self.serial) else 0
         changed = wg != self._coop_wg
@@ -497,10 +520,6 @@ class PipelinedIteration(object):
                 self._capture(mode, k)
             torch.cuda.synchronize(self.dev)
 
-    def _bind_carry(self, p):
-        p.state, p.hxs, p.cxs = self.carry["state"], self.carry["hxs"], self.carry["cxs"]
-        p.done, p.eps_len = self.carry["done"], self.carry["eps_len"]
-
     def _capture(self, mode, k):
         p, args = self.players[k], self.args
         torch.cuda.synchronize(self.dev)
@@ -509,22 +528,14 @@ class PipelinedIteration(object):
         torch.cuda.synchronize(self.dev)
         g_r = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g_r, capture_error_mode="thread_local"):
-            self._bind_carry(p)
-            p.carry_out, p.carry_written = self.carry, ()             # the rollout's epilogue kernel publishes the carry
-            rollout(p, args.num_steps)
-            for key, src in (("state", p.state), ("hxs", p.hxs.detach()), ("cxs", p.cxs.detach()), ("done", p.done),
-                             ("eps_len", p.eps_len)):
-                if key in p.carry_written:
-                    continue
-                if self.carry[key].data_ptr() != src.data_ptr():
-                    self.carry[key].copy_(src)
-            p.carry_out = None
+            with self._carried(p):
+                rollout(p, args.num_steps)
+            # (the carry copies of _carried come here: before the join)
             if hasattr(p.env, "generator_join"):
                 p.env.generator_join()        # the env's forked generator launches (opt-in) end inside the captured region
         # the learner of THIS rollout reads the replica's own end-of-rollout tensors (last observation slot, LSTM state, done):
         # the carry belongs to the next rollout by then
         g_l = torch.cuda.CUDAGraph()
-        from . import fused
         with fused.gemm_tn_corun(self.corun), torch.cuda.graph(g_l, capture_error_mode="thread_local"):
             if PREGROW_MODE != "off" and hasattr(p.env, "pregrow"):
                 # the Maze maps the NEXT rollouts' generator passes will ask for, grown on the learner's stream beside the
@@ -608,14 +619,9 @@ class PipelinedIteration(object):
 
     def _schedule_tensors(self):
         """Every tensor an update of this schedule writes: master weights, optimizer state, the replicas' weight copies."""
-        opt = self.optimizer
-        seen, out = set(), []
-        for t in [opt.bucket.flat, opt.bucket.grad] + [v for v in vars(opt).values() if isinstance(v, torch.Tensor)] \
-                + [b.flat for b in self.buckets]:
-            if t.data_ptr() not in seen and t.numel() > 0:
-                seen.add(t.data_ptr())
-                out.append(t)
-        return out
+        return update_tensors(self.optimizer, [b.flat for b in self.buckets], grad=True)
+
+    _written = _schedule_tensors
 
     def burn_in(self, iters, mode=None):
         """GraphedIteration.burn_in for this schedule: `iters` (rounded up to whole phase pairs) iterations whose updates are
@@ -623,22 +629,69 @@ class PipelinedIteration(object):
         restored; the env shard and the carried LSTM state move on. tune_streams() has this effect as well (its trial
         iterations are rolled back the same way), which is why the two-stream schedule looked like the better LEARNER in
         round 4's seed table: it was the only one whose envs had drifted apart before training began."""
-        if iters <= 0:
-            return
+        i0 = self.i
+        super().burn_in(int(iters) + (int(iters) & 1), mode)
+        self.i = i0
+
+    def _ranks_agree(self, candidates, iters, partitions):
+        """tune_streams, multi-rank: every trial holds collectives, so the ranks must agree on what they are about to do BEFORE
+        any of them leaves: a rank with serial=True (or another forced CU split, another candidate count — per-rank environment
+        variables) would return early while the others wait in an all-reduce for ever."""
+        cfg = torch.tensor([1 if self.serial else 0, int(self.cu_split), int(candidates), -1 if iters is None else int(iters),
+                            len(partitions)],
+                           dtype=torch.int64, device=self.dev)
+        lo, hi = cfg.clone(), cfg.clone()
+        dist.all_reduce(lo, op=dist.ReduceOp.MIN)
+        dist.all_reduce(hi, op=dist.ReduceOp.MAX)
+        if not torch.equal(lo, hi):
+            raise RuntimeError("PipelinedIteration.tune_streams: ranks disagree on (serial, cu_split, candidates, iters, "
+                               "partitions): min %s max %s — set ATR_PIPE_CU_SPLIT / the schedule identically on every rank"
+                               % (lo.tolist(), hi.tolist()))
+
+    def _stream_candidates(self, candidates, partitions, multi):
+        """tune_streams: [(rollout stream, learner stream, label)] to try, the pair in use first. Multi-rank: one all-reduce
+        per entry of `partitions`, made or not."""
+        pairs = [(self.sR, self.sL, "as constructed")]
+        if self.cu_split:
+            return pairs
+        pairs += [(self.sR, torch.cuda.Stream(device=self.dev), "learner stream %d" % (c + 1)) for c in range(candidates)]
+        total = device_cus(self.dev)
+        for part in partitions:
+            made = None
+            try:
+                if part == "half":
+                    halves = cu_partition(self.dev)
+                    if halves is not None:
+                        (r0, rn), (l0, ln) = halves
+                        made = (cu_masked_stream(self.dev, r0, rn, total), cu_masked_stream(self.dev, l0, ln, total),
+                                "CU partition %d / %d" % (rn, ln))
+                elif 0 < int(part) < total:
+                    r_cus = int(part)
+                    made = (cu_masked_stream(self.dev, total - r_cus, r_cus, total),
+                            cu_masked_stream(self.dev, 0, total - r_cus, total), "CU partition %d / %d" % (r_cus, total - r_cus))
+            except (RuntimeError, OSError, AttributeError, ValueError):   # a runtime without CU masks
+                made = None
+            if multi:       # the candidate exists on every rank or on none
+                ok = torch.tensor([1 if made is not None else 0], dtype=torch.int32, device=self.dev)
+                dist.all_reduce(ok, op=dist.ReduceOp.MIN)
+                if int(ok.item()) == 0:
+                    made = None
+            if made is not None:
+                pairs.append(made)
+        return pairs
+
+    def _time_phases(self, settle, iters):
+        """ms per phase on the host clock: `settle` phases to fill the pipeline, drained, then `iters` timed ones, drained."""
+        for _ in range(settle):
+            self.run()
         self.finish()
         torch.cuda.synchronize(self.dev)
-        tensors = self._schedule_tensors()
-        saved = [t.clone() for t in tensors]
-        i0, n0 = self.i, self.master.n_steps
-        for _ in range(int(iters) + (int(iters) & 1)):
-            self.run(mode)
+        t0 = time.perf_counter()
+        for _ in range(iters):
+            self.run()
         self.finish()
         torch.cuda.synchronize(self.dev)
-        with torch.no_grad():
-            for t, v in zip(tensors, saved):
-                t.copy_(v)
-        self.i, self.master.n_steps = i0, n0
-        torch.cuda.synchronize(self.dev)
+        return (time.perf_counter() - t0) / iters * 1e3
 
     def tune_streams(self, candidates=4, iters=None, partitions=("half",), keep_updates=False):
         """Pick the stream pair the two chains overlap best on. Two things are not in the application's hands and are settled
@@ -664,108 +717,47 @@ class PipelinedIteration(object):
         candidates are kept only if every rank has them, all-reduce MIN) and must KEEP the same pair (the per-candidate times
         are all-reduced MAX — an iteration is as slow as its slowest rank — before the argmin).
         Returns [(ms per iteration, chosen, label)] per candidate."""
-        import time as _time
-        import torch.distributed as dist
         multi = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
         if multi:
-            # Every trial below holds collectives, so the ranks must agree on what they are about to do BEFORE any of them
-            # leaves: a rank with serial=True (or another forced CU split, another candidate count — per-rank environment
-            # variables) would return here while the others wait in an all-reduce for ever.
-            cfg = torch.tensor([1 if self.serial else 0, int(self.cu_split), int(candidates), -1 if iters is None else int(iters),
-                                len(partitions)],
-                               dtype=torch.int64, device=self.dev)
-            lo, hi = cfg.clone(), cfg.clone()
-            dist.all_reduce(lo, op=dist.ReduceOp.MIN)
-            dist.all_reduce(hi, op=dist.ReduceOp.MAX)
-            if not torch.equal(lo, hi):
-                raise RuntimeError("PipelinedIteration.tune_streams: ranks disagree on (serial, cu_split, candidates, iters, "
-                                   "partitions): min %s max %s — set ATR_PIPE_CU_SPLIT / the schedule identically on every rank"
-                                   % (lo.tolist(), hi.tolist()))
+            self._ranks_agree(candidates, iters, partitions)
         if self.serial:
             return []
-        pairs = [(self.sR, self.sL, "as constructed")]
-        if not self.cu_split:
-            pairs += [(self.sR, torch.cuda.Stream(device=self.dev), "learner stream %d" % (c + 1)) for c in range(candidates)]
-            total = device_cus(self.dev)
-            for part in partitions:
-                made = None
-                try:
-                    if part == "half":
-                        halves = cu_partition(self.dev)
-                        if halves is not None:
-                            (r0, rn), (l0, ln) = halves
-                            made = (cu_masked_stream(self.dev, r0, rn, total), cu_masked_stream(self.dev, l0, ln, total),
-                                    "CU partition %d / %d" % (rn, ln))
-                    elif 0 < int(part) < total:
-                        r_cus = int(part)
-                        made = (cu_masked_stream(self.dev, total - r_cus, r_cus, total),
-                                cu_masked_stream(self.dev, 0, total - r_cus, total), "CU partition %d / %d" % (r_cus, total - r_cus))
-                except (RuntimeError, OSError, AttributeError, ValueError):   # a runtime without CU masks
-                    made = None
-                if multi:       # the candidate exists on every rank or on none
-                    ok = torch.tensor([1 if made is not None else 0], dtype=torch.int32, device=self.dev)
-                    dist.all_reduce(ok, op=dist.ReduceOp.MIN)
-                    if int(ok.item()) == 0:
-                        made = None
-                if made is not None:
-                    pairs.append(made)
+        pairs = self._stream_candidates(candidates, partitions, multi)
         self.finish()
         torch.cuda.synchronize(self.dev)
-        tensors = None if keep_updates else self._schedule_tensors()
-        saved = [t.clone() for t in tensors] if tensors is not None else None
         i0, n0 = self.i, self.master.n_steps
-        # A trial must be long enough for the steady state to show: one call of run() is one PHASE, a trial starts with an empty
-        # pipeline and ends with finish(), and at 512 envs eight iterations are 10 ms of which the fill / drain is a fifth — the
-        # CU partition (1.13 ms per iteration in steady state against 1.24 on shared streams) then only TIES its trial and loses
-        # it every other run (one collection pass of round 5: 8.3 M instead of 9.1). So the trial length is set from a pilot: ~50 ms per
-        # candidate, 8 to 64 iterations (the same on every rank: the pilot time is all-reduced MAX), unless the caller fixes `iters`.
-        if iters is None:
-            self._use_streams(pairs[0][0], pairs[0][1])
-            for _ in range(2):
-                self.run()
+        with rolled_back(None if keep_updates else self._schedule_tensors()):
+            # A trial must be long enough for the steady state to show: one call of run() is one PHASE, a trial starts with an empty
+            # pipeline and ends with finish(), and at 512 envs eight iterations are 10 ms of which the fill / drain is a fifth — the
+            # CU partition (1.13 ms per iteration in steady state against 1.24 on shared streams) then only TIES its trial and loses
+            # it every other run (one collection pass of round 5: 8.3 M instead of 9.1). So the trial length is set from a pilot: ~50 ms per
+            # candidate, 8 to 64 iterations (the same on every rank: the pilot time is all-reduced MAX), unless the caller fixes `iters`.
+            if iters is None:
+                self._use_streams(pairs[0][0], pairs[0][1])
+                pilot_ms = self._time_phases(2, 4)
+                if multi:
+                    pm = torch.tensor([pilot_ms], dtype=torch.float64, device=self.dev)
+                    dist.all_reduce(pm, op=dist.ReduceOp.MAX)
+                    pilot_ms = float(pm.item())
+                iters = max(8, min(64, int(50.0 / max(pilot_ms, 1e-3))))
+            iters += iters & 1              # whole pairs of phases per candidate: the replica parity is the same afterwards
+            # two passes over the list, the better of a candidate's two times counts: one 8-iteration sample is noisy enough to
+            # lose the CU partition its trial at 512 envs in two runs of six (8.2 M env steps/s instead of 8.9)
+            times = [float("inf")] * len(pairs)
+            for _pass in range(2):
+                for j, (sR, sL, label) in enumerate(pairs):
+                    self._use_streams(sR, sL)
+                    times[j] = min(times[j], self._time_phases(2, iters))
             self.finish()
             torch.cuda.synchronize(self.dev)
-            t0 = _time.perf_counter()
-            for _ in range(4):
-                self.run()
-            self.finish()
-            torch.cuda.synchronize(self.dev)
-            pilot_ms = (_time.perf_counter() - t0) / 4 * 1e3
             if multi:
-                pm = torch.tensor([pilot_ms], dtype=torch.float64, device=self.dev)
-                dist.all_reduce(pm, op=dist.ReduceOp.MAX)
-                pilot_ms = float(pm.item())
-            iters = max(8, min(64, int(50.0 / max(pilot_ms, 1e-3))))
-        iters += iters & 1              # whole pairs of phases per candidate: the replica parity is the same afterwards
-        # two passes over the list, the better of a candidate's two times counts: one 8-iteration sample is noisy enough to
-        # lose the CU partition its trial at 512 envs in two runs of six (8.2 M env steps/s instead of 8.9)
-        times = [float("inf")] * len(pairs)
-        for _pass in range(2):
-            for j, (sR, sL, label) in enumerate(pairs):
-                self._use_streams(sR, sL)
-                for _ in range(2):
-                    self.run()
-                self.finish()
-                torch.cuda.synchronize(self.dev)
-                t0 = _time.perf_counter()
-                for _ in range(iters):
-                    self.run()
-                self.finish()
-                torch.cuda.synchronize(self.dev)
-                times[j] = min(times[j], (_time.perf_counter() - t0) / iters * 1e3)
-        self.finish()
-        torch.cuda.synchronize(self.dev)
-        if multi:
-            tt = torch.tensor(times, dtype=torch.float64, device=self.dev)
-            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-            times = tt.tolist()
-        best = min(range(len(pairs)), key=lambda j: times[j])
-        self._use_streams(pairs[best][0], pairs[best][1])
-        self.stream_choice = pairs[best][2]
-        if saved is not None:
-            with torch.no_grad():
-                for t, v in zip(tensors, saved):
-                    t.copy_(v)
+                tt = torch.tensor(times, dtype=torch.float64, device=self.dev)
+                dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+                times = tt.tolist()
+            best = min(range(len(pairs)), key=lambda j: times[j])
+            self._use_streams(pairs[best][0], pairs[best][1])
+            self.stream_choice = pairs[best][2]
+        if not keep_updates:
             assert (self.i - i0) % 2 == 0      # (pilot 2 + 4, each candidate 2 x (2 + iters) phases: replica i0 & 1 is next, as before)
             self.i, self.master.n_steps = i0, n0
             torch.cuda.synchronize(self.dev)
@@ -775,7 +767,6 @@ class PipelinedIteration(object):
 def sync_train_modes(train_modes, device, src=0):
     """Every rank must differentiate the same loss before the all-reduce: rank `src` (the only one running the
     evaluator, which owns the schedule — test.py:84-92,129-134) broadcasts its train_modes list."""
-    import torch.distributed as dist
     if not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
         return train_modes
     t = torch.tensor([int(m) for m in train_modes], dtype=torch.int64, device=device)

@@ -64,24 +64,7 @@ for sched in a.schedules:
                 it.tune_streams()
         else:
             it = GraphedIteration(player, opt, args)
-        if a.burn_in > 0:
-            tensors = it._schedule_tensors() if pipelined else it._optimizer_tensors()
-            saved = [t.clone() for t in tensors]
-            i0 = getattr(it, "i", 0)
-            n0 = (it.master if pipelined else player).n_steps
-            for _ in range(a.burn_in + (a.burn_in & 1)):
-                it.run()
-            if pipelined:
-                it.finish()
-            torch.cuda.synchronize()
-            with torch.no_grad():
-                for t, v in zip(tensors, saved):
-                    t.copy_(v)
-            if pipelined:
-                it.i, it.master.n_steps = i0, n0
-            else:
-                player.n_steps = n0
-            torch.cuda.synchronize()
+        it.burn_in(a.burn_in)
         rew_acc = torch.zeros(2, device=dev)
         row, t0 = [], time.time()
         for i in range(1, a.iters + 1):

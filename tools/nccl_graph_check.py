@@ -22,7 +22,7 @@ player, opt = make_player(args, dev)
 it = GraphedIteration(player, opt, args)
 t0 = time.time()
 for i in range(30):
-    it.g_roll.replay()
+    it.g_rolls[it.mode0].replay()
     dist.all_reduce(opt.bucket.grad, op=dist.ReduceOp.SUM)
     opt.bucket.grad.div_(1)
     it.g_opt.replay()
