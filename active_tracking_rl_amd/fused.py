@@ -1,5 +1,7 @@
 """ctypes + autograd bindings of the policy-side HIP kernels (include/atr_policy.h). GPU tensors only — on CPU tensors the
 model evaluates the same network with plain PyTorch ops (model.CNN_maze.forward_dense_stem / forward_conv2d, nn.LSTMCell).
+The header's ABI is declared once: ATR_STRUCTS (its structs) and ATR_PROTOTYPES (its functions); lib() applies the table and
+every launch goes through it, so a launch status other than 0 raises RuntimeError from one place (_errcheck).
 
   stem / stem_into / stem_into2 / stem_cached   CNN_maze's conv(1->16,k3,s2,p1)+ReLU+conv(16->32,k3,s2,p1)+ReLU on
                                                 13x13 frames: one launch forward, two backward (csrc/stem_hip.hip)
@@ -13,6 +15,10 @@ model evaluates the same network with plain PyTorch ops (model.CNN_maze.forward_
                                                 matrix cores (csrc/gemm_tn_hip.hip)
   linear_relu_cached, lstm_sequence_cached      cached-forward autograd nodes of the rollout cache (model.RolloutCache)"""
 import ctypes as C
+import json
+import os
+import re
+import sys
 
 import torch
 
@@ -78,119 +84,116 @@ class GemmTnProblem(C.Structure):
                 ("N", C.c_int), ("ld1", C.c_longlong), ("ld2", C.c_longlong)]
 
 
+class RolloutConsts(C.Structure):
+    """atr_rollout_consts of include/atr_policy.h."""
+    _fields_ = [("w_ih", C.c_void_p * 2), ("w_hh", C.c_void_p * 2), ("b_ih", C.c_void_p * 2), ("b_hh", C.c_void_p * 2),
+                ("bsum", C.c_void_p), ("w_cat", C.c_void_p), ("fa_w", C.c_void_p), ("fa_b", C.c_void_p), ("emb_ih", C.c_void_p),
+                ("counter", C.c_void_p), ("fh0", C.c_void_p), ("fh_pstride", C.c_longlong), ("fh_ld", C.c_longlong),
+                ("F", C.c_int), ("A_act", C.c_int)]
+
+
+ATR_STRUCTS = {"atr_act_step": ActStepArgs, "atr_coop_step": CoopStepArgs, "atr_linear_args": LinearArgs,
+               "atr_gate_cell_args": GateCellArgs, "atr_pair_linear_args": PairLinearArgs, "atr_heads_loss_args": HeadsLossArgs,
+               "atr_gemm_tn_problem": GemmTnProblem, "atr_rollout_consts": RolloutConsts}
+VALUE = "value"     # marks an int result that is not a launch status (or whose non-zero value the caller handles): no errcheck
+
+
+def _prototypes():
+    """{entry point: (restype, [argtypes]) or (restype, [argtypes], VALUE)} for every function include/atr_policy.h declares,
+    called from Python or not (tests/test_abi_cpu.py holds the table and the structs above to the header)."""
+    vp, cp, ll, i32, u32, u64, f32, f64 = (C.c_void_p, C.c_char_p, C.c_longlong, C.c_int, C.c_uint, C.c_ulonglong, C.c_float,
+                                           C.c_double)
+    ptr = C.POINTER
+    stem_fwd = [vp, ll, vp, vp, vp, vp, vp, ll]                     # one stem problem: x, x_stride, w1, b1, w2, b2, y, M
+    stem_bwd = [vp, ll] + [vp] * 10 + [ll, vp]
+    draw = [vp, vp, u64, u32, i32, i32, vp]                         # actions_out, counter, seed, ordinal, N, R, stream
+    bptt_pre = [vp, vp, vp, vp, ll, vp, vp, vp, i32, i32, vp, ll, vp, ll, vp, vp, vp, ll, vp, vp]
+    begin = [vp, vp, vp, vp, ll, vp, vp, ll, i32, i32, i32]
+    end = [vp, vp, ll, vp, vp, vp, vp, vp, i32, i32, i32, i32]
+    linear = ptr(LinearArgs)
+    return {
+        "atr_stem_forward": (i32, stem_fwd + [vp]),
+        "atr_stem_forward2": (i32, stem_fwd * 2 + [vp]),
+        "atr_stem_workspace_floats": (ll, [ll]),
+        "atr_stem_backward": (i32, stem_bwd),
+        "atr_stem_forward_u8": (i32, stem_fwd + [vp]),
+        "atr_stem_forward2_u8": (i32, stem_fwd * 2 + [vp]),
+        "atr_stem_backward_u8": (i32, stem_bwd),
+        "atr_sample_actions": (i32, [vp, vp, vp, vp, vp, u64, u32, i32, i32, i32, i32, vp]),
+        "atr_lstm_cell_forward": (i32, [vp, vp, vp, vp, ll, vp, vp, vp, ll, vp, ll, vp, ll, i32, i32, i32, vp]),
+        "atr_lstm_cell_forward_act": (i32, [vp] * 11 + [i32] + draw),
+        "atr_lstm_cell_forward_act1": (i32, [vp] * 12 + [i32] + draw),
+        "atr_lstm_cell_forward_act2": (i32, [vp] * 5 + [ll, vp, vp, ll, vp, ll, vp, ll] + [vp] * 4 + [i32] + draw),
+        "atr_gate_cell": (i32, [ptr(GateCellArgs), vp]),
+        "atr_gate_cell_workgroups": (i32, [i32], VALUE),
+        "atr_act_env_step": (i32, [vp, ptr(ActStepArgs), vp, i32, vp, vp, vp]),
+        "atr_coop_env_step": (i32, [vp, ptr(ActStepArgs), ptr(CoopStepArgs), vp, i32, vp, vp, vp]),
+        "atr_lt_init": (i32, [cp], VALUE),                          # (the next candidate path is tried)
+        "atr_linear": (i32, [linear, vp]),
+        "atr_linear_plan_info": (i32, [linear, ptr(i32), ptr(i32), ptr(i32), ptr(f32), ptr(i32), ptr(i32)], VALUE),
+        "atr_linear_set_choice": (i32, [linear, i32, i32], VALUE),  # (ignored in linear_lt, raised in linear_lt_set_choice)
+        "atr_lt_library_info": (i32, [ptr(i32), ptr(i32), cp, i32], VALUE),
+        "atr_linear_kernel_name": (i32, [linear, cp, i32], VALUE),
+        "atr_lt_last_error": (cp, []),
+        "atr_pair_linear": (i32, [ptr(PairLinearArgs), vp]),
+        "atr_actor_step": (i32, [vp] * 12 + [i32, i32, i32, vp]),
+        "atr_lstm_cell_backward": (i32, [vp, ll, vp, vp, vp, vp, vp, ll, vp, ll, vp, ll, vp, ll, i32, i32, i32, i32, vp]),
+        "atr_lstm_bptt": (i32, [vp, vp, vp, vp, ll, vp, ll, vp, vp, vp, ll, vp, vp, i32, i32, i32, i32, vp]),
+        "atr_lstm_bptt_pre": (i32, bptt_pre + [i32, i32, i32, i32, vp]),
+        "atr_lstm_bptt_act_sums_floats": (ll, [i32]),
+        "atr_lstm_bptt_pre2": (i32, bptt_pre + [vp, i32, i32, i32, i32, vp]),
+        "atr_embed_fold": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]),
+        "atr_embed_add": (i32, [vp, vp, vp, vp, ll, ll, ll, vp, ll, i32, i32, vp]),
+        "atr_embed_add_ld": (i32, [vp, ll, vp, vp, vp, ll, ll, ll, vp, ll, i32, i32, vp]),
+        "atr_relu_backward_ld": (i32, [vp, vp, ll, vp, ll, i32, vp]),
+        "atr_embed_grad_workspace_floats": (ll, [ll, i32, i32]),
+        "atr_embed_grad": (i32, [vp, vp, ll, ll, ll, vp, vp, vp, ll, i32, i32, vp]),
+        "atr_gae_returns": (i32, [vp, vp, vp, f32, f32, vp, vp, i32, i32, i32, vp]),
+        "atr_heads_values": (i32, [vp, vp, vp, vp, ll, i32, i32, i32, vp]),
+        "atr_heads_values2": (i32, [vp, vp, vp, i32, vp, vp, vp, i32, vp, ll, i32, i32, vp]),
+        "atr_heads_workspace_floats": (ll, [ll, i32, i32]),
+        "atr_heads_loss": (i32, [vp, vp, vp, vp, vp, i32, i32, vp, i32, i32, vp, vp, vp, vp, vp, f32, f32, f32, vp, vp, vp, ll,
+                                 i32, i32, vp]),
+        "atr_heads_loss_multi": (i32, [ptr(HeadsLossArgs), i32, f32, vp]),
+        "atr_gemm_tn_workspace_floats": (ll, [ll, i32, i32]),
+        "atr_gemm_tn": (i32, [vp, vp, vp, vp, ll, i32, i32, vp, vp, vp]),
+        "atr_scatter_segments": (i32, [ptr(vp), ptr(ll), ptr(i32), i32, vp, vp]),
+        "atr_gemm_tn_grouped_workspace_floats": (ll, [ptr(GemmTnProblem), i32, ll]),
+        "atr_gemm_tn_set_corun": (i32, [i32], VALUE),               # (returns the previous mode)
+        "atr_gemm_tn_grouped": (i32, [ptr(GemmTnProblem), i32, ll, vp, vp]),
+        "atr_rollout_begin": (i32, begin + [vp]),
+        "atr_rollout_begin2": (i32, begin + [ptr(RolloutConsts), vp]),
+        "atr_rollout_end": (i32, end + [vp]),
+        "atr_rollout_end2": (i32, end + [vp, vp, ll, vp, vp]),
+        "atr_adam_step": (i32, [vp] * 7 + [f64] * 5 + [i32, ll, vp]),
+        "atr_rmsprop_step": (i32, [vp] * 3 + [f64] * 4 + [ll, vp]),
+    }
+
+
+ATR_PROTOTYPES = _prototypes()
+# the library's own text for a failed launch, where it keeps one
+_ERROR_DETAIL = {"atr_act_env_step": "t2d_last_error", "atr_coop_env_step": "t2d_last_error", "atr_linear": "atr_lt_last_error"}
+
+
+def _errcheck(name):
+    """The ctypes errcheck of a status-returning entry point: a non-zero status raises, 0 is handed back to the caller."""
+    def check(status, func=None, args=None):
+        if status != 0:
+            detail = ": " + getattr(lib(), _ERROR_DETAIL[name])().decode() if name in _ERROR_DETAIL else ""
+            raise RuntimeError("%s failed (%d)%s" % (name, status, detail))
+        return status
+    return check
+
+
 def lib():
     global _lib
     if _lib is None:
         L = vec_env.load_library()
-        vp, ll = C.c_void_p, C.c_longlong
-        L.atr_stem_forward.restype = C.c_int
-        L.atr_stem_forward.argtypes = [vp, ll, vp, vp, vp, vp, vp, ll, vp]
-        L.atr_stem_forward2.restype = C.c_int
-        L.atr_stem_forward2.argtypes = [vp, ll, vp, vp, vp, vp, vp, ll] * 2 + [vp]
-        L.atr_stem_workspace_floats.restype = ll
-        L.atr_stem_workspace_floats.argtypes = [ll]
-        L.atr_stem_backward.restype = C.c_int
-        L.atr_stem_backward.argtypes = [vp, ll] + [vp] * 10 + [ll, vp]
-        for name in ("atr_stem_forward", "atr_stem_forward2", "atr_stem_backward"):      # the u8-frame twins
-            f = getattr(L, name + "_u8")
-            f.restype, f.argtypes = C.c_int, getattr(L, name).argtypes
-        L.atr_sample_actions.restype = C.c_int
-        L.atr_sample_actions.argtypes = [vp, vp, vp, vp, vp, C.c_ulonglong, C.c_uint, C.c_int, C.c_int, C.c_int, C.c_int, vp]
-        i32 = C.c_int
-        L.atr_lstm_cell_forward.restype = i32
-        L.atr_lstm_cell_forward.argtypes = [vp, vp, vp, vp, ll, vp, vp, vp, ll, vp, ll, vp, ll, i32, i32, i32, vp]
-        L.atr_lstm_cell_forward_act.restype = i32
-        L.atr_lstm_cell_forward_act.argtypes = [vp] * 11 + [i32, vp, vp, C.c_ulonglong, C.c_uint, i32, i32, vp]
-        L.atr_lstm_cell_forward_act1.restype = i32
-        L.atr_lstm_cell_forward_act1.argtypes = [vp] * 12 + [i32, vp, vp, C.c_ulonglong, C.c_uint, i32, i32, vp]
-        L.atr_lstm_cell_forward_act2.restype = i32
-        L.atr_lstm_cell_forward_act2.argtypes = [vp] * 5 + [ll, vp, vp, ll, vp, ll, vp, ll] + [vp] * 4 + [i32, vp, vp,
-                                                 C.c_ulonglong, C.c_uint, i32, i32, vp]
-        L.atr_embed_add.restype = i32
-        L.atr_embed_add.argtypes = [vp, vp, vp, vp, ll, ll, ll, vp, ll, i32, i32, vp]
-        L.atr_embed_add_ld.restype = i32
-        L.atr_embed_add_ld.argtypes = [vp, ll, vp, vp, vp, ll, ll, ll, vp, ll, i32, i32, vp]
-        L.atr_relu_backward_ld.restype = i32
-        L.atr_relu_backward_ld.argtypes = [vp, vp, ll, vp, ll, i32, vp]
-        L.atr_lt_init.restype = i32
-        L.atr_lt_init.argtypes = [C.c_char_p]
-        L.atr_linear.restype = i32
-        L.atr_linear.argtypes = [C.POINTER(LinearArgs), vp]
-        L.atr_linear_plan_info.restype = i32
-        L.atr_linear_plan_info.argtypes = [C.POINTER(LinearArgs), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32),
-                                           C.POINTER(C.c_float), C.POINTER(i32), C.POINTER(i32)]
-        L.atr_linear_set_choice.restype = i32
-        L.atr_linear_set_choice.argtypes = [C.POINTER(LinearArgs), i32, i32]
-        L.atr_lt_library_info.restype = i32
-        L.atr_lt_library_info.argtypes = [C.POINTER(i32), C.POINTER(i32), C.c_char_p, i32]
-        L.atr_linear_kernel_name.restype = i32
-        L.atr_linear_kernel_name.argtypes = [C.POINTER(LinearArgs), C.c_char_p, i32]
-        L.atr_lt_last_error.restype = C.c_char_p
-        L.atr_embed_grad_workspace_floats.restype = ll
-        L.atr_embed_grad_workspace_floats.argtypes = [ll, i32, i32]
-        L.atr_embed_grad.restype = i32
-        L.atr_embed_grad.argtypes = [vp, vp, ll, ll, ll, vp, vp, vp, ll, i32, i32, vp]
-        L.atr_lstm_bptt.restype = i32
-        L.atr_lstm_bptt.argtypes = [vp, vp, vp, vp, ll, vp, ll, vp, vp, vp, ll, vp, vp, i32, i32, i32, i32, vp]
-        L.atr_gate_cell.restype = i32
-        L.atr_gate_cell.argtypes = [C.POINTER(GateCellArgs), vp]
-        L.atr_gate_cell_workgroups.restype = i32
-        L.atr_gate_cell_workgroups.argtypes = [i32]
-        L.atr_lstm_bptt_pre2.restype = i32
-        L.atr_lstm_bptt_pre2.argtypes = [vp, vp, vp, vp, ll, vp, vp, vp, i32, i32, vp, ll, vp, ll, vp, vp, vp, ll, vp, vp, vp,
-                                         i32, i32, i32, i32, vp]
-        L.atr_lstm_bptt_act_sums_floats.restype = ll
-        L.atr_lstm_bptt_act_sums_floats.argtypes = [i32]
-        L.atr_embed_fold.restype = i32
-        L.atr_embed_fold.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]
-        L.atr_lstm_bptt_pre.restype = i32
-        L.atr_lstm_bptt_pre.argtypes = [vp, vp, vp, vp, ll, vp, vp, vp, i32, i32, vp, ll, vp, ll, vp, vp, vp, ll, vp, vp,
-                                        i32, i32, i32, i32, vp]
-        L.atr_pair_linear.restype = i32
-        L.atr_pair_linear.argtypes = [C.POINTER(PairLinearArgs), vp]
-        L.atr_act_env_step.restype = i32
-        L.atr_act_env_step.argtypes = [vp, C.POINTER(ActStepArgs), vp, i32, vp, vp, vp]
-        L.atr_coop_env_step.restype = i32
-        L.atr_coop_env_step.argtypes = [vp, C.POINTER(ActStepArgs), C.POINTER(CoopStepArgs), vp, i32, vp, vp, vp]
-        L.atr_actor_step.restype = i32
-        L.atr_actor_step.argtypes = [vp] * 12 + [i32, i32, i32, vp]
-        L.atr_lstm_cell_backward.restype = i32
-        L.atr_lstm_cell_backward.argtypes = [vp, ll, vp, vp, vp, vp, vp, ll, vp, ll, vp, ll, vp, ll, i32, i32, i32, i32, vp]
-        L.atr_heads_values.restype = i32
-        L.atr_heads_values.argtypes = [vp, vp, vp, vp, ll, i32, i32, i32, vp]
-        L.atr_heads_values2.restype = i32
-        L.atr_heads_values2.argtypes = [vp, vp, vp, i32, vp, vp, vp, i32, vp, ll, i32, i32, vp]
-        L.atr_heads_loss_multi.restype = i32
-        L.atr_heads_loss_multi.argtypes = [C.POINTER(HeadsLossArgs), i32, C.c_float, vp]
-        L.atr_heads_workspace_floats.restype = ll
-        L.atr_heads_workspace_floats.argtypes = [ll, i32, i32]
-        L.atr_heads_loss.restype = i32
-        L.atr_heads_loss.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp, i32, i32, vp, vp, vp, vp, vp, C.c_float, C.c_float,
-                                     C.c_float, vp, vp, vp, ll, i32, i32, vp]
-        L.atr_gemm_tn_workspace_floats.restype = ll
-        L.atr_gemm_tn_workspace_floats.argtypes = [ll, i32, i32]
-        L.atr_gemm_tn.restype = i32
-        L.atr_gemm_tn.argtypes = [vp, vp, vp, vp, ll, i32, i32, vp, vp, vp]
-        L.atr_gemm_tn_grouped_workspace_floats.restype = ll
-        L.atr_gemm_tn_grouped_workspace_floats.argtypes = [C.POINTER(GemmTnProblem), i32, ll]
-        L.atr_gemm_tn_set_corun.restype = i32
-        L.atr_gemm_tn_set_corun.argtypes = [i32]
-        L.atr_gemm_tn_grouped.restype = i32
-        L.atr_gemm_tn_grouped.argtypes = [C.POINTER(GemmTnProblem), i32, ll, vp, vp]
-        L.atr_scatter_segments.restype = i32
-        L.atr_scatter_segments.argtypes = [C.POINTER(C.c_void_p), C.POINTER(ll), C.POINTER(i32), i32, vp, vp]
-        L.atr_gae_returns.restype = i32
-        L.atr_gae_returns.argtypes = [vp, vp, vp, C.c_float, C.c_float, vp, vp, i32, i32, i32, vp]
-        L.atr_rollout_begin.restype = i32
-        L.atr_rollout_begin.argtypes = [vp, vp, vp, vp, ll, vp, vp, ll, i32, i32, i32, vp]
-        L.atr_rollout_end.restype = i32
-        L.atr_rollout_end.argtypes = [vp, vp, ll, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
-        L.atr_rollout_end2.restype = i32
-        L.atr_rollout_end2.argtypes = [vp, vp, ll, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, ll, vp, vp]
-        L.atr_adam_step.restype = i32
-        L.atr_adam_step.argtypes = [vp] * 7 + [C.c_double] * 5 + [i32, ll, vp]
-        L.atr_rmsprop_step.restype = i32
-        L.atr_rmsprop_step.argtypes = [vp] * 3 + [C.c_double] * 4 + [ll, vp]
+        for name, (restype, argtypes, *value) in ATR_PROTOTYPES.items():
+            f = getattr(L, name)
+            f.restype, f.argtypes = restype, argtypes
+            if restype is C.c_int and not value:
+                f.errcheck = _errcheck(name)
         _lib = L
     return _lib
 
@@ -215,14 +218,10 @@ def _stream(t):
 class _Stem(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w1, b1, w2, b2):
-        if x.stride(1) != 1 or x.stride(0) < 169:      # rows must be contiguous; the row stride is free
-            x = x.contiguous()
         w1c, b1c, w2c, b2c = w1.contiguous(), b1.contiguous(), w2.contiguous(), b2.contiguous()
         M = x.shape[0]
         y = torch.empty((M, 512), dtype=torch.float32, device=x.device)
-        rc = _stem_fn("atr_stem_forward", x)(_p(x), x.stride(0), _p(w1c), _p(b1c), _p(w2c), _p(b2c), _p(y), M, _stream(x))
-        if rc != 0:
-            raise RuntimeError("atr_stem_forward failed (%d)" % rc)
+        _stem_fn("atr_stem_forward", x)(_p(x), x.stride(0), _p(w1c), _p(b1c), _p(w2c), _p(b2c), _p(y), M, _stream(x))
         ctx.save_for_backward(x, y, w1c, b1c, w2c)
         ctx.shapes = (w1.shape, w2.shape)
         return y
@@ -240,10 +239,8 @@ def _stem_backward(x, y, dy, w1, b1, w2, shapes):
     ws = torch.empty(L.atr_stem_workspace_floats(M), dtype=torch.float32, device=x.device)
     dw1, db1 = torch.empty(144, device=x.device), torch.empty(16, device=x.device)
     dw2, db2 = torch.empty(4608, device=x.device), torch.empty(32, device=x.device)
-    rc = _stem_fn("atr_stem_backward", x)(_p(x), x.stride(0), _p(y), _p(dy), _p(w1), _p(b1), _p(w2), _p(dw1), _p(db1),
-                                          _p(dw2), _p(db2), _p(ws), M, _stream(x))
-    if rc != 0:
-        raise RuntimeError("atr_stem_backward failed (%d)" % rc)
+    _stem_fn("atr_stem_backward", x)(_p(x), x.stride(0), _p(y), _p(dy), _p(w1), _p(b1), _p(w2), _p(dw1), _p(db1),
+                                     _p(dw2), _p(db2), _p(ws), M, _stream(x))
     return dw1.view(shapes[0]), db1, dw2.view(shapes[1]), db2
 
 
@@ -267,44 +264,30 @@ class _StemCached(torch.autograd.Function):
 @torch.no_grad()
 def stem_into(x, conv1, conv2, out):
     """No-grad stem forward of frames x [..., 13, 13] written into out [M, 512] (a slot of the rollout cache)."""
-    x = rows169(x)
-    if x.stride(1) != 1 or x.stride(0) < 169:
-        x = x.contiguous()
+    x = _frame_rows(x)
     M = x.shape[0]
     assert out.is_contiguous() and out.numel() == M * 512
-    rc = _stem_fn("atr_stem_forward", x)(_p(x), x.stride(0), _p(conv1.weight), _p(conv1.bias), _p(conv2.weight),
-                                         _p(conv2.bias), _p(out), M, _stream(x))
-    if rc != 0:
-        raise RuntimeError("atr_stem_forward failed (%d)" % rc)
+    _stem_fn("atr_stem_forward", x)(_p(x), x.stride(0), _p(conv1.weight), _p(conv1.bias), _p(conv2.weight),
+                                    _p(conv2.bias), _p(out), M, _stream(x))
     return out
 
 
 @torch.no_grad()
 def stem_into2(xa, enc_a, out_a, xb, enc_b, out_b):
     """stem_into for two encoders (different weights) in one launch: the rollout step's tracker and target stems."""
-    xs = []
-    for x in (xa, xb):
-        x = rows169(x)
-        if x.stride(1) != 1 or x.stride(0) < 169:
-            x = x.contiguous()
-        xs.append(x)
+    xs = [_frame_rows(xa), _frame_rows(xb)]
     args = []
     for x, enc, out in ((xs[0], enc_a, out_a), (xs[1], enc_b, out_b)):
         assert out.is_contiguous() and out.numel() == x.shape[0] * 512
         args += [_p(x), x.stride(0), _p(enc.conv1.weight), _p(enc.conv1.bias), _p(enc.conv2.weight), _p(enc.conv2.bias),
                  _p(out), x.shape[0]]
     assert xs[0].dtype == xs[1].dtype
-    rc = _stem_fn("atr_stem_forward2", xs[0])(*(args + [_stream(xs[0])]))
-    if rc != 0:
-        raise RuntimeError("atr_stem_forward2 failed (%d)" % rc)
+    _stem_fn("atr_stem_forward2", xs[0])(*(args + [_stream(xs[0])]))
     return out_a, out_b
 
 
 def stem_cached(x, y, conv1, conv2):
-    x = rows169(x)
-    if x.stride(1) != 1 or x.stride(0) < 169:
-        x = x.contiguous()
-    return _StemCached.apply(x, y, conv1.weight, conv1.bias, conv2.weight, conv2.bias)
+    return _StemCached.apply(_frame_rows(x), y, conv1.weight, conv1.bias, conv2.weight, conv2.bias)
 
 
 class _LinearReluCached(torch.autograd.Function):
@@ -340,9 +323,7 @@ def relu_backward_ld(df, f):
     """df * (f > 0) for a dense df [rows, C] and an activation f [rows, C] whose rows are f.stride(0) floats apart."""
     rows, Cc = df.shape
     out = torch.empty_like(df)
-    rc = lib().atr_relu_backward_ld(_p(df), _p(f), f.stride(0), _p(out), rows, Cc, _stream(df))
-    if rc != 0:
-        raise RuntimeError("atr_relu_backward_ld failed (%d)" % rc)
+    lib().atr_relu_backward_ld(_p(df), _p(f), f.stride(0), _p(out), rows, Cc, _stream(df))
     return out
 
 
@@ -354,7 +335,6 @@ def _lt_init():
     global _lt_ready
     if _lt_ready:
         return
-    import os
     cands = [os.path.join(os.path.dirname(torch.__file__), "lib", "libhipblaslt.so")]
     try:
         for ln in open("/proc/self/maps"):
@@ -384,7 +364,6 @@ def lt_available():
             _lt_init()
             _lt_state = True
         except (RuntimeError, OSError) as ex:
-            import sys
             print("active_tracking_rl_amd: hipBLASLt direct path unavailable (%s); using the torch GEMM path" % (ex,), file=sys.stderr)
             _lt_state = False
     return _lt_state
@@ -410,8 +389,7 @@ def _linear_args(a, w, out, bias, relu, workspace):
     return g
 
 
-LT_TUNING_FILE = __import__("os").path.join(__import__("os").path.dirname(__import__("os").path.abspath(__file__)),
-                                            "lt_tuning_gfx950.json")
+LT_TUNING_FILE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lt_tuning_gfx950.json")
 LT_SOURCES = {0: "none", 1: "timed", 2: "recorded", 3: "first-usable", 4: "refused", 5: "refused-timed"}
 _lt_choices, _lt_seen, _lt_status = None, {}, "not loaded"
 
@@ -429,7 +407,6 @@ def _lt_family(key):
     same products), but hipBLASLt's heuristic takes the stride into account and a timing run can crown another tile shape,
     whose fp32 sums differ in the last bit: two runs of one seed then part ways at the first sampled action. So the kernel is
     chosen per FAMILY: every output stride runs the choice recorded (or first timed) for the family."""
-    import re
     return re.sub(r"_sc\d+", "", key)
 
 
@@ -437,7 +414,6 @@ def _lt_family_choices():
     """{family: (candidate index, solution index)}: of a family's records the one with the largest output stride (the rollout
     store at the bench's rollout length — the default path)."""
     fam = {}
-    import re
     for k, v in lt_choices().items():
         sc = int(re.search(r"_sc(\d+)", k).group(1)) if re.search(r"_sc(\d+)", k) else 0
         f = _lt_family(k)
@@ -469,8 +445,6 @@ def lt_choices():
     solution index against the list it gets."""
     global _lt_choices, _lt_status
     if _lt_choices is None:
-        import json
-        import os
         _lt_choices = {}
         if os.environ.get("ATR_LT_TUNING", "1") == "0":
             _lt_status = "timed at first use (ATR_LT_TUNING=0)"
@@ -550,8 +524,7 @@ def linear_lt(a, w, out, bias=None, relu=False, workspace=None):
         rec = _lt_family_choices().get(fam) or _lt_family_first.get(fam)
         if rec is not None:
             L.atr_linear_set_choice(C.byref(g), rec[0], rec[1])
-    if L.atr_linear(C.byref(g), _stream(a)) != 0:
-        raise RuntimeError("atr_linear failed: %s" % L.atr_lt_last_error().decode())
+    L.atr_linear(C.byref(g), _stream(a))
     if fresh and rec is None:
         info = _plan_info(g)
         # (only a TIMED choice is handed to the family's other strides: a first-usable plan made inside a stream capture is
@@ -592,9 +565,17 @@ def rows169(x):
     return x.reshape(m, 169)
 
 
+def _frame_rows(x):
+    """rows169(x) as the stem kernels read it: rows must be contiguous, the row stride is free (>= 169); else a copy."""
+    x = rows169(x)
+    if x.stride(1) != 1 or x.stride(0) < 169:
+        x = x.contiguous()
+    return x
+
+
 def stem(x, conv1, conv2):
     """x: frames [..., 13, 13] float32 on the GPU (any evenly strided view) -> [M, 512]."""
-    return _Stem.apply(rows169(x), conv1.weight, conv1.bias, conv2.weight, conv2.bias)
+    return _Stem.apply(_frame_rows(x), conv1.weight, conv1.bias, conv2.weight, conv2.bias)
 
 
 class ActionSampler(object):
@@ -616,10 +597,8 @@ class ActionSampler(object):
             self._ordinal = 0
             return
         dummy = self.counter
-        rc = lib().atr_sample_actions(_p(dummy), _p(dummy), _p(dummy), _p(dummy), _p(self.counter), self.seed, 0, 1,
-                                      0, 4, 1, _stream(self.counter))
-        if rc != 0:
-            raise RuntimeError("atr_sample_actions failed (%d)" % rc)
+        lib().atr_sample_actions(_p(dummy), _p(dummy), _p(dummy), _p(dummy), _p(self.counter), self.seed, 0, 1,
+                                 0, 4, 1, _stream(self.counter))
         self._ordinal = 0
 
     def end_block(self):
@@ -644,10 +623,8 @@ class ActionSampler(object):
         else:
             self._ordinal += 1
             ordinal, bump = self._ordinal, 0
-        rc = lib().atr_sample_actions(_p(h), _p(linear.weight), _p(linear.bias), _p(actions), _p(self.counter),
-                                      self.seed, ordinal, bump, n, R, A, _stream(h))
-        if rc != 0:
-            raise RuntimeError("atr_sample_actions failed (%d)" % rc)
+        lib().atr_sample_actions(_p(h), _p(linear.weight), _p(linear.bias), _p(actions), _p(self.counter),
+                                 self.seed, ordinal, bump, n, R, A, _stream(h))
         return actions
 
 
@@ -661,10 +638,8 @@ def lstm_cell(ig, hg, c_prev, keep=None, done=None):
     is applied inside. Returns (h, c) [N,R]."""
     N, R = c_prev.shape
     h, c = torch.empty_like(c_prev), torch.empty_like(c_prev)
-    rc = lib().atr_lstm_cell_forward(_p(ig), None, _p(hg), _p(c_prev), 0, _pn(keep), _pn(done), _p(h), 0, _p(c), 0,
-                                     None, 0, 1, N, R, _stream(ig))
-    if rc != 0:
-        raise RuntimeError("atr_lstm_cell_forward failed (%d)" % rc)
+    lib().atr_lstm_cell_forward(_p(ig), None, _p(hg), _p(c_prev), 0, _pn(keep), _pn(done), _p(h), 0, _p(c), 0,
+                                None, 0, 1, N, R, _stream(ig))
     return h, c
 
 
@@ -695,13 +670,11 @@ class _LstmSeq(torch.autograd.Function):
         for t in range(T):
             torch.bmm(h_all[:, t], whh, out=hg)
             off = t * N * 4 * R * 4
-            rc = L.atr_lstm_cell_forward(
+            L.atr_lstm_cell_forward(
                 C.c_void_p(ig0.data_ptr() + off), C.c_void_p(ig1.data_ptr() + off) if ig1 is not None else None,
                 _p(hg), C.c_void_p(c_all.data_ptr() + t * step), ps, _p(keep[t - 1]) if t else None, None,
                 C.c_void_p(h_all.data_ptr() + (t + 1) * step), ps, C.c_void_p(c_all.data_ptr() + (t + 1) * step), ps,
                 C.c_void_p(acts.data_ptr() + t * astep), pa, P, N, R, st)
-            if rc != 0:
-                raise RuntimeError("atr_lstm_cell_forward failed (%d)" % rc)
         ctx.save_for_backward(whh, keep, h_all, c_all, acts)
         ctx.two = ig1 is not None
         c_last = c_all[:, T].clone()                                             # un-masked final cell state
@@ -731,6 +704,16 @@ def activate_preacts(pre, info):
                         torch.sigmoid(x[..., 3, :])], -2).reshape(P, T, N, R4).contiguous()
 
 
+def _fused_bptt_ok(h_all, *stores):
+    """Whether the one-launch BPTT (csrc/bptt_hip.hip) can run: switched on, R = 128, on the GPU, `stores` contiguous."""
+    return use_fused_bptt and h_all.shape[-1] == 128 and h_all.is_cuda and all(t.is_contiguous() for t in stores)
+
+
+def _keep_prev(keep):
+    """keep [T, N] shifted by one step: the mask on h_{t-1} (ones for step 0, whose previous state comes masked)."""
+    return torch.cat([torch.ones_like(keep[:1]), keep[:-1]], 0)
+
+
 def _lstm_bptt(whh, keep, h_all, c_all, acts, dhs, whh_nn=None, want_dwhh=True, pre=None):
     """Back-propagation through time over stored activations: dhs = per-player dL/dh_seq [T,N,R] (None = zero).
     Returns dG [P, T*N, 4R] (= dL/d ig), dL/dh0, dL/dc0 [P,N,R] and dL/dW_hh^T [P,R,4R]. whh_nn: per-player weight_hh [4R,R]
@@ -742,8 +725,7 @@ def _lstm_bptt(whh, keep, h_all, c_all, acts, dhs, whh_nn=None, want_dwhh=True, 
     P, T1, N, R = h_all.shape
     T = T1 - 1
     dev = h_all.device
-    fused_ok = (use_fused_bptt and R == 128 and h_all.is_cuda and acts.is_contiguous() and c_all.is_contiguous()
-                and keep.is_contiguous())
+    fused_ok = _fused_bptt_ok(h_all, acts, c_all, keep)
     if pre is not None and not fused_ok:
         acts, pre = activate_preacts(acts, pre), None
     dG = torch.empty((P, T, N, 4 * R), dtype=torch.float32, device=dev)
@@ -772,32 +754,28 @@ def _lstm_bptt(whh, keep, h_all, c_all, acts, dhs, whh_nn=None, want_dwhh=True, 
                 # per row tile of the embedding's player: column sums of dG by the row's tracker action (see embed_fold)
                 sums = torch.empty(L.atr_lstm_bptt_act_sums_floats(N), dtype=torch.float32, device=dev)
             pre["act_sums"] = sums
-            rc = L.atr_lstm_bptt_pre2(_pn(dh_c[0]), _pn(dh_c[1]) if P > 1 else None, _p(keep), _p(acts), acts.stride(0),
-                                      _p(bias[0]), _p(bias[1]) if P > 1 else None, _pn(emb), ep, n_act, _pn(act), act_ts,
-                                      _p(c_all), ps, _p(whh_nn[0]), _p(whh_nn[1]) if P > 1 else None, _p(dG), pa, _p(dhn),
-                                      _p(dcc), _pn(sums), P, T, N, R, st)
+            L.atr_lstm_bptt_pre2(_pn(dh_c[0]), _pn(dh_c[1]) if P > 1 else None, _p(keep), _p(acts), acts.stride(0),
+                                 _p(bias[0]), _p(bias[1]) if P > 1 else None, _pn(emb), ep, n_act, _pn(act), act_ts,
+                                 _p(c_all), ps, _p(whh_nn[0]), _p(whh_nn[1]) if P > 1 else None, _p(dG), pa, _p(dhn),
+                                 _p(dcc), _pn(sums), P, T, N, R, st)
         else:
-            rc = L.atr_lstm_bptt(_pn(dh_c[0]), _pn(dh_c[1]) if P > 1 else None, _p(keep), _p(acts), pa, _p(c_all), ps,
-                                 _p(whh_nn[0]), _p(whh_nn[1]) if P > 1 else None, _p(dG), pa, _p(dhn), _p(dcc), P, T, N, R, st)
-        if rc != 0:
-            raise RuntimeError("atr_lstm_bptt failed (%d)" % rc)
+            L.atr_lstm_bptt(_pn(dh_c[0]), _pn(dh_c[1]) if P > 1 else None, _p(keep), _p(acts), pa, _p(c_all), ps,
+                            _p(whh_nn[0]), _p(whh_nn[1]) if P > 1 else None, _p(dG), pa, _p(dhn), _p(dcc), P, T, N, R, st)
     else:
         dhs = [torch.zeros((T, N, R), dtype=torch.float32, device=dev) if d is None else d.contiguous() for d in dhs]
         pd = (dhs[1].data_ptr() - dhs[0].data_ptr()) // 4 if P > 1 else 0          # player stride between the two grads
         whh_t = whh.transpose(1, 2)                                               # [P,4R,R]
         for t in range(T - 1, -1, -1):
-            rc = L.atr_lstm_cell_backward(
+            L.atr_lstm_cell_backward(
                 C.c_void_p(dhs[0].data_ptr() + t * step), pd, _p(dhn), _p(dcc), _p(keep[t]),
                 _p(keep[t - 1]) if t else None, C.c_void_p(acts.data_ptr() + t * astep), pa,
                 C.c_void_p(c_all.data_ptr() + (t + 1) * step), ps, C.c_void_p(c_all.data_ptr() + t * step), ps,
                 C.c_void_p(dG.data_ptr() + t * astep), pa, 1 if t < T - 1 else 0, P, N, R, st)
-            if rc != 0:
-                raise RuntimeError("atr_lstm_cell_backward failed (%d)" % rc)
             torch.bmm(dG[:, t], whh_t, out=dhn)                                   # gradient into h_{t-1}
     if not want_dwhh:          # (the caller registers dW_hh with the grouped weight-gradient launch)
         return dG.view(P, T * N, 4 * R), dhn, dcc, None
     # W_hh: sum_t (k_{t-1} h_{t-1})^T dG_t as one GEMM per player over all T*N rows
-    kprev = torch.cat([torch.ones_like(keep[:1]), keep[:-1]], 0)              # [T, N]: mask on h_{t-1}
+    kprev = _keep_prev(keep)
     dG = dG.view(P, T * N, 4 * R)
     if use_gemm_tn and R % 128 == 0 and T * N >= 4096:
         # the mask is applied to h's rows on their way into the GEMM kernel's LDS tiles
@@ -819,8 +797,7 @@ class _LstmSeqCached(torch.autograd.Function):
         P = h_all.shape[0]
         feats, wih, whh_l = fw[:P], fw[P:2 * P], fw[2 * P:3 * P]
         # ([P, R, 4R] transposed copy: only the per-step fallback recurrence reads it — the fused BPTT kernel takes weight_hh as is)
-        fused_path = use_fused_bptt and h_all.shape[-1] == 128 and h_all.is_cuda
-        whh = h_all.new_empty(0) if fused_path else torch.stack([w.t() for w in whh_l], 0).contiguous()
+        whh = h_all.new_empty(0) if _fused_bptt_ok(h_all) else torch.stack([w.t() for w in whh_l], 0).contiguous()
         ctx.save_for_backward(keep.contiguous(), h_all, c_all, acts, whh, *feats, *wih, *whh_l, *fw[3 * P:5 * P], *fw[5 * P:])
         ctx.P = P
         ctx.fold = len(fw) == 5 * P + 2           # fc_action_tracker's weight and bias ride along: the embedding is folded
@@ -841,8 +818,7 @@ class _LstmSeqCached(torch.autograd.Function):
         db2 = None
         q = _deferred
         T, N, R = h_all.shape[1] - 1, h_all.shape[2], h_all.shape[3]
-        if whh.numel() == 0 and not (use_fused_bptt and R == 128 and acts.is_contiguous() and c_all.is_contiguous()
-                                     and keep.is_contiguous()):
+        if whh.numel() == 0 and not _fused_bptt_ok(h_all, acts, c_all, keep):     # (empty whh: forward saw h_all on the GPU)
             whh = torch.stack([w.t() for w in whh_nn], 0).contiguous()
         if all(ctx.need):
             groups = [list(range(P))]
@@ -887,7 +863,7 @@ class _LstmSeqCached(torch.autograd.Function):
                         continue
                     if r1 is not None:         # (cannot happen for R = 128; keep the queue consistent if it ever does)
                         raise RuntimeError("grouped weight gradients: dW_hh could not join the group after dW_ih did")
-                    kprev = torch.cat([torch.ones_like(keep[:1]), keep[:-1]], 0).reshape(T * N)
+                    kprev = _keep_prev(keep).reshape(T * N)
                     dwhh_l[p] = gemm_tn(h_all[p, :T].reshape(T * N, R), dG[i], row_scale=kprev).t()
                     dwih[p], db[p] = gemm_tn(dG[i], feats[p], colsum=True)
                     if p == fold_p:
@@ -915,10 +891,8 @@ def embed_fold(act_sums, fa_w, fa_b, wih, dwih, dfa_w, dfa_b):
     assert fa_w.shape == (Cc, 4) and fa_w.is_contiguous() and fa_b.is_contiguous() and wih.is_contiguous() and dwih.is_contiguous()
     assert dwih.shape == (J, Cc) and act_sums.numel() % (4 * J) == 0
     S = torch.empty((4, J), dtype=torch.float32, device=wih.device)
-    rc = lib().atr_embed_fold(_p(act_sums), act_sums.numel() // (4 * J), _p(fa_w), _p(fa_b), _p(wih), _p(dwih), _p(dfa_w), _p(dfa_b),
-                              _p(S), J, Cc, _stream(wih))
-    if rc != 0:
-        raise RuntimeError("atr_embed_fold failed (%d)" % rc)
+    lib().atr_embed_fold(_p(act_sums), act_sums.numel() // (4 * J), _p(fa_w), _p(fa_b), _p(wih), _p(dwih), _p(dfa_w), _p(dfa_b),
+                         _p(S), J, Cc, _stream(wih))
 
 
 def lstm_sequence_cached(lstms, feats, keep, h_all, c_all, acts, need=None, hm=None, pre=None, fold=None):
@@ -938,22 +912,19 @@ def lstm_sequence_cached(lstms, feats, keep, h_all, c_all, acts, need=None, hm=N
 def embed_fold_ok(pre, h_all, c_all, keep, fa):
     """Whether lstm_sequence_cached can fold the tracker-action embedding (the fused BPTT launch over stored pre-activations,
     the four-move action table, parameters as the kernels read them)."""
-    return bool(fold_embedding and pre is not None and pre.get("emb") is not None and use_fused_bptt and h_all.is_cuda
-                and h_all.shape[-1] == 128 and c_all.is_contiguous() and keep.is_contiguous()
+    return bool(fold_embedding and pre is not None and pre.get("emb") is not None and _fused_bptt_ok(h_all, c_all, keep)
                 and fa.weight.shape[1] == 4 and fa.weight.is_contiguous() and fa.weight.data_ptr() % 16 == 0)
 
 
-fold_embedding = __import__("os").environ.get("ATR_FOLD_EMBEDDING", "1") != "0"
+fold_embedding = os.environ.get("ATR_FOLD_EMBEDDING", "1") != "0"
 
 
 @torch.no_grad()
 def lstm_cell_into(ig, hg, c_prev, done, h_out, c_out, acts):
     """The rollout's LSTM step for one player, writing h, c and the activated gates into rollout-cache slots."""
     N, R = c_prev.shape
-    rc = lib().atr_lstm_cell_forward(_p(ig), None, _p(hg), _p(c_prev), 0, None, _pn(done), _p(h_out), 0, _p(c_out), 0,
-                                     _p(acts), 0, 1, N, R, _stream(ig))
-    if rc != 0:
-        raise RuntimeError("atr_lstm_cell_forward failed (%d)" % rc)
+    lib().atr_lstm_cell_forward(_p(ig), None, _p(hg), _p(c_prev), 0, None, _pn(done), _p(h_out), 0, _p(c_out), 0,
+                                _p(acts), 0, 1, N, R, _stream(ig))
 
 
 @torch.no_grad()
@@ -967,13 +938,11 @@ def lstm_cell_act2_into(ig, hg, biases, c_prev, done, h_out, c_out, acts, sample
         assert t.stride(-1) == 1 and t.stride(-2) == t.shape[-1]
     ordinal = sampler._ordinal + 1
     sampler._ordinal += 2
-    rc = lib().atr_lstm_cell_forward_act2(
+    lib().atr_lstm_cell_forward_act2(
         _p(ig), _p(hg), _p(biases[0]), _p(biases[1]), _p(c_prev), c_prev.stride(0), _pn(done), _p(h_out), h_out.stride(0),
         _p(c_out), c_out.stride(0), _pn(acts), acts.stride(0) if acts is not None else 0, _p(actors[0].weight),
         _p(actors[0].bias), _p(actors[1].weight), _p(actors[1].bias), actors[0].weight.shape[0], _p(actions_out),
         _p(sampler.counter), sampler.seed, ordinal, N, R, _stream(ig))
-    if rc != 0:
-        raise RuntimeError("atr_lstm_cell_forward_act2 failed (%d)" % rc)
     return actions_out
 
 
@@ -988,17 +957,15 @@ def lstm_cell_act_into(ig, hg, c_prev, done, h_out, c_out, acts, sampler, actor,
     assert sampler._ordinal is not None
     sampler._ordinal += 1
     if bias is not None:
-        rc = lib().atr_lstm_cell_forward_act1(_p(ig), _p(hg), _p(bias), _p(c_prev), _pn(done), _p(h_out), _p(c_out),
-                                              _pn(acts), _pn(emb), _pn(act_in), _p(actor.weight), _p(actor.bias),
-                                              actor.weight.shape[0], _p(actions_out), _p(sampler.counter), sampler.seed,
-                                              sampler._ordinal, N, R, _stream(ig))
+        lib().atr_lstm_cell_forward_act1(_p(ig), _p(hg), _p(bias), _p(c_prev), _pn(done), _p(h_out), _p(c_out),
+                                         _pn(acts), _pn(emb), _pn(act_in), _p(actor.weight), _p(actor.bias),
+                                         actor.weight.shape[0], _p(actions_out), _p(sampler.counter), sampler.seed,
+                                         sampler._ordinal, N, R, _stream(ig))
     else:
-        rc = lib().atr_lstm_cell_forward_act(_p(ig), _p(hg), _p(c_prev), _pn(done), _p(h_out), _p(c_out), _pn(acts),
-                                             _pn(emb), _pn(act_in), _p(actor.weight), _p(actor.bias), actor.weight.shape[0],
-                                             _p(actions_out), _p(sampler.counter), sampler.seed, sampler._ordinal, N, R,
-                                             _stream(ig))
-    if rc != 0:
-        raise RuntimeError("atr_lstm_cell_forward_act failed (%d)" % rc)
+        lib().atr_lstm_cell_forward_act(_p(ig), _p(hg), _p(c_prev), _pn(done), _p(h_out), _p(c_out), _pn(acts),
+                                        _pn(emb), _pn(act_in), _p(actor.weight), _p(actor.bias), actor.weight.shape[0],
+                                        _p(actions_out), _p(sampler.counter), sampler.seed, sampler._ordinal, N, R,
+                                        _stream(ig))
     return actions_out
 
 
@@ -1028,10 +995,43 @@ def pair_linear(a1, w1, out, bias=None, a2=None, w2=None, done=None, relu=False)
         g.c[p], g.ldc[p] = _rows(out[p])
     g.done = done.data_ptr() if done is not None else None
     g.M, g.N, g.relu = M, N, 1 if relu else 0
-    rc = lib().atr_pair_linear(C.byref(g), _stream(a1[0]))
-    if rc != 0:
-        raise RuntimeError("atr_pair_linear failed (%d)" % rc)
+    lib().atr_pair_linear(C.byref(g), _stream(a1[0]))
     return out
+
+
+def _act_step_args(ig, hg, biases, c_prev, done, h_out, c_out, acts, sampler, actors, actions_out, emb, hm_out):
+    """atr_act_step for act_env_step / coop_env_step (their arguments; ig / hg / biases / acts: None, or None per player).
+    Takes the sampler's next two ordinals."""
+    N, R = h_out[0].shape
+    assert sampler._ordinal is not None and actions_out.is_contiguous() and actions_out.shape == (2, N)
+    ig, hg, biases, acts = (ts if ts is not None else (None, None) for ts in (ig, hg, biases, acts))
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    a = ActStepArgs()
+    for p in range(2):
+        for t in (ig[p], c_prev[p], h_out[p], c_out[p]):
+            assert t is None or (t.is_contiguous() and t.dtype == torch.float32)
+        assert (hg[p] is None or hg[p].is_contiguous()) and (acts[p] is None or acts[p].is_contiguous())
+        # (ig[0] None: the tracker's cell already ran as the epilogue of the step's gate product, fused.gate_cell)
+        a.ig[p], a.hg[p], a.bias[p], a.acts[p] = ptr(ig[p]), ptr(hg[p]), ptr(biases[p]), ptr(acts[p])
+        a.c_prev[p], a.h_out[p], a.c_out[p] = ptr(c_prev[p]), h_out[p].data_ptr(), ptr(c_out[p])
+        a.actor_w[p], a.actor_b[p] = actors[p].weight.data_ptr(), actors[p].bias.data_ptr()
+    a.emb, a.done_prev = ptr(emb), ptr(done)
+    a.actions_out, a.counter, a.seed = actions_out.data_ptr(), sampler.counter.data_ptr(), sampler.seed
+    a.ordinal = sampler._ordinal + 1
+    sampler._ordinal += 2
+    a.A, a.N, a.R = actors[0].weight.shape[0], N, R
+    if hm_out is not None:
+        assert hm_out[0].shape == (N, R) and hm_out[1].shape == (N, R)
+        assert hm_out[0].stride(1) == 1 and hm_out[1].stride(1) == 1 and hm_out[0].stride(0) == hm_out[1].stride(0)
+        a.hm_out[0], a.hm_out[1], a.hm_ld = hm_out[0].data_ptr(), hm_out[1].data_ptr(), hm_out[0].stride(0)
+    return a
+
+
+def _env_out_args(env_out):
+    """(obs, obs_is_u8, rew, done) of the env-stepping launches from env_out = (obs u8 | f32, rew, done)."""
+    obs, rew, done_out = env_out
+    assert obs.is_contiguous() and rew.is_contiguous() and done_out.is_contiguous() and obs.dtype in (torch.uint8, torch.float32)
+    return _p(obs), 1 if obs.dtype == torch.uint8 else 0, _p(rew), _p(done_out)
 
 
 @torch.no_grad()
@@ -1045,42 +1045,12 @@ def act_env_step(env_core, ig, hg, biases, c_prev, done, h_out, c_out, acts, sam
     hm_out (with the env step only): per-player [N,R] views with a common row stride — they receive the fresh hidden rows
     zeroed where this step's done flag is set (what the next step's LSTMCell GEMM reads).
     Same results as lstm_cell_act_into x 2 + env.step. Only valid inside sampler.begin_block(); consumes two ordinals."""
-    N, R = h_out[0].shape
-    assert sampler._ordinal is not None and actions_out.is_contiguous() and actions_out.shape == (2, N)
-    a = ActStepArgs()
-    for p in range(2):
-        for t in (ig[p], c_prev[p], h_out[p], c_out[p]):
-            assert t is None or (t.is_contiguous() and t.dtype == torch.float32)
-        # (ig[0] None: the tracker's cell already ran as the epilogue of the step's gate product, fused.gate_cell)
-        a.ig[p] = ig[p].data_ptr() if ig[p] is not None else None
-        a.hg[p] = hg[p].data_ptr() if hg is not None and hg[p] is not None else None
-        a.bias[p] = biases[p].data_ptr() if biases is not None and biases[p] is not None else None
-        a.c_prev[p] = c_prev[p].data_ptr() if c_prev[p] is not None else None
-        a.h_out[p], a.c_out[p] = h_out[p].data_ptr(), (c_out[p].data_ptr() if c_out[p] is not None else None)
-        a.acts[p] = acts[p].data_ptr() if acts is not None and acts[p] is not None else None
-        assert hg is None or hg[p] is None or hg[p].is_contiguous()
-        assert acts is None or acts[p] is None or acts[p].is_contiguous()
-        a.actor_w[p], a.actor_b[p] = actors[p].weight.data_ptr(), actors[p].bias.data_ptr()
-    a.emb = emb.data_ptr() if emb is not None else None
-    a.done_prev = done.data_ptr() if done is not None else None
-    a.actions_out, a.counter, a.seed = actions_out.data_ptr(), sampler.counter.data_ptr(), sampler.seed
-    a.ordinal = sampler._ordinal + 1
-    sampler._ordinal += 2
-    a.A, a.N, a.R = actors[0].weight.shape[0], N, R
-    if hm_out is not None:
-        assert env_core is not None and hm_out[0].shape == (N, R) and hm_out[1].shape == (N, R)
-        assert hm_out[0].stride(1) == 1 and hm_out[1].stride(1) == 1 and hm_out[0].stride(0) == hm_out[1].stride(0)
-        a.hm_out[0], a.hm_out[1], a.hm_ld = hm_out[0].data_ptr(), hm_out[1].data_ptr(), hm_out[0].stride(0)
-    L = lib()
+    assert hm_out is None or env_core is not None
+    a = _act_step_args(ig, hg, biases, c_prev, done, h_out, c_out, acts, sampler, actors, actions_out, emb, hm_out)
     if env_core is None:
-        rc = L.atr_act_env_step(None, C.byref(a), None, 0, None, None, _stream(h_out[0]))
+        lib().atr_act_env_step(None, C.byref(a), None, 0, None, None, _stream(h_out[0]))
     else:
-        obs, rew, done_out = env_out
-        assert obs.is_contiguous() and rew.is_contiguous() and done_out.is_contiguous() and obs.dtype in (torch.uint8, torch.float32)
-        rc = L.atr_act_env_step(env_core.h, C.byref(a), _p(obs), 1 if obs.dtype == torch.uint8 else 0, _p(rew), _p(done_out),
-                                _stream(h_out[0]))
-    if rc != 0:
-        raise RuntimeError("atr_act_env_step failed (%d): %s" % (rc, L.t2d_last_error().decode()))
+        lib().atr_act_env_step(env_core.h, C.byref(a), *_env_out_args(env_out), _stream(h_out[0]))
     return actions_out
 
 
@@ -1105,9 +1075,7 @@ def gate_cell(fh, w_cat, biases, pre, c_prev, done, h_out, c_out, cell=(True, Fa
     a.done_prev = done.data_ptr() if done is not None else None
     a.lda, a.N, a.K, a.R = fh.stride(1), N, K, w_cat.shape[1] // 4
     a.probe = probe.data_ptr() if probe is not None else None
-    rc = lib().atr_gate_cell(C.byref(a), _stream(fh))
-    if rc != 0:
-        raise RuntimeError("atr_gate_cell failed (%d)" % rc)
+    lib().atr_gate_cell(C.byref(a), _stream(fh))
 
 
 _stream_cus = {}
@@ -1150,39 +1118,20 @@ def coop_env_step(env_core, ys, fcs, fh_t, w_cat, gates, biases, c_prev, done, h
     envs end to end; `workgroups` = the CUs the launch's stream may use (all of them must be free to be resident at once)."""
     N, R = c_prev[0].shape
     Fd = fcs[0].weight.shape[0]
-    assert sampler._ordinal is not None and actions_out.is_contiguous() and actions_out.shape == (2, N)
     assert fh_t.shape == (2, N, Fd + R) and fh_t.stride(2) == 1 and fh_t.stride(1) == Fd + R
     assert w_cat.is_contiguous() and w_cat.shape == (2, 4 * R, Fd + R) and gates.is_contiguous() and gates.shape == (2, N, 4 * R)
-    a, k = ActStepArgs(), CoopStepArgs()
+    k = CoopStepArgs()
     for p in range(2):
         for t in (c_prev[p], h_out[p], c_out[p], biases[p], ys[p]):
             assert t.is_contiguous() and t.dtype == torch.float32
         assert ys[p].shape == (N, fcs[p].weight.shape[1]) and fcs[p].weight.is_contiguous() and fcs[p].weight.shape[0] == Fd
-        a.ig[p], a.hg[p], a.bias[p] = None, None, biases[p].data_ptr()
-        a.c_prev[p], a.h_out[p], a.c_out[p] = c_prev[p].data_ptr(), h_out[p].data_ptr(), c_out[p].data_ptr()
-        a.acts[p] = acts[p].data_ptr() if acts is not None and acts[p] is not None else None
-        assert acts is None or acts[p] is None or acts[p].is_contiguous()
-        a.actor_w[p], a.actor_b[p] = actors[p].weight.data_ptr(), actors[p].bias.data_ptr()
         k.y[p], k.ldy[p], k.kfc[p] = ys[p].data_ptr(), ys[p].stride(0), ys[p].shape[1]
         k.fc_w[p], k.fc_b[p], k.w_cat[p] = fcs[p].weight.data_ptr(), fcs[p].bias.data_ptr(), w_cat[p].data_ptr()
-    a.emb = emb.data_ptr() if emb is not None else None
-    a.done_prev = done.data_ptr() if done is not None else None
-    a.actions_out, a.counter, a.seed = actions_out.data_ptr(), sampler.counter.data_ptr(), sampler.seed
-    a.ordinal = sampler._ordinal + 1
-    sampler._ordinal += 2
-    a.A, a.N, a.R = actors[0].weight.shape[0], N, R
-    assert hm_out[0].shape == (N, R) and hm_out[1].shape == (N, R)
-    assert hm_out[0].stride(1) == 1 and hm_out[1].stride(1) == 1 and hm_out[0].stride(0) == hm_out[1].stride(0)
-    a.hm_out[0], a.hm_out[1], a.hm_ld = hm_out[0].data_ptr(), hm_out[1].data_ptr(), hm_out[0].stride(0)
+    assert hm_out is not None
+    a = _act_step_args(None, None, biases, c_prev, done, h_out, c_out, acts, sampler, actors, actions_out, emb, hm_out)
     k.fh, k.gates, k.fh_pstride, k.fh_ld, k.F, k.workgroups = fh_t.data_ptr(), gates.data_ptr(), fh_t.stride(0), Fd + R, Fd, int(workgroups)
     k.probe = COOP_PROBE.data_ptr() if COOP_PROBE is not None else None
-    obs, rew, done_out = env_out
-    assert obs.is_contiguous() and rew.is_contiguous() and done_out.is_contiguous() and obs.dtype in (torch.uint8, torch.float32)
-    L = lib()
-    rc = L.atr_coop_env_step(env_core.h, C.byref(a), C.byref(k), _p(obs), 1 if obs.dtype == torch.uint8 else 0, _p(rew), _p(done_out),
-                             _stream(gates))
-    if rc != 0:
-        raise RuntimeError("atr_coop_env_step failed (%d): %s" % (rc, L.t2d_last_error().decode()))
+    lib().atr_coop_env_step(env_core.h, C.byref(a), C.byref(k), *_env_out_args(env_out), _stream(gates))
     return actions_out
 
 
@@ -1198,10 +1147,8 @@ def actor_step_into(f, h_prev, c_prev, done, lstm, bias, h_out, c_out, acts, emb
     N, F = f.shape
     R = h_prev.shape[1]
     assert f.is_contiguous() and h_prev.is_contiguous() and c_prev.is_contiguous() and h_out.is_contiguous() and c_out.is_contiguous()
-    rc = lib().atr_actor_step(_p(f), _p(h_prev), _p(c_prev), _pn(done), _p(lstm.weight_ih), _p(lstm.weight_hh), _p(bias),
-                              _pn(emb), _pn(act_in), _p(h_out), _p(c_out), _pn(acts), N, F, R, _stream(f))
-    if rc != 0:
-        raise RuntimeError("atr_actor_step failed (%d)" % rc)
+    lib().atr_actor_step(_p(f), _p(h_prev), _p(c_prev), _pn(done), _p(lstm.weight_ih), _p(lstm.weight_hh), _p(bias),
+                         _pn(emb), _pn(act_in), _p(h_out), _p(c_out), _pn(acts), N, F, R, _stream(f))
     return h_out, c_out
 
 
@@ -1215,11 +1162,14 @@ def gae_returns(rewards, values, notdone, gamma, tau):
     T, N, A = rewards.shape[0], rewards.shape[1], rewards.shape[2]
     rewards, values, notdone = rewards.contiguous(), values.contiguous(), notdone.contiguous()
     ret, gae = torch.empty_like(rewards), torch.empty_like(rewards)
-    rc = lib().atr_gae_returns(_p(rewards), _p(values), _p(notdone), float(gamma), float(tau), _p(ret), _p(gae),
-                               T, N, A, _stream(rewards))
-    if rc != 0:
-        raise RuntimeError("atr_gae_returns failed (%d)" % rc)
+    lib().atr_gae_returns(_p(rewards), _p(values), _p(notdone), float(gamma), float(tau), _p(ret), _p(gae),
+                          T, N, A, _stream(rewards))
     return ret, gae
+
+
+def _col_stride(t):
+    """Floats between consecutive rows of a [..., A] or [..., A, 1] store whose column the heads kernels address: A."""
+    return t.shape[-2] if t.shape[-1] == 1 else t.shape[-1]
 
 
 @torch.no_grad()
@@ -1228,10 +1178,8 @@ def heads_values(h, critic, values, off):
     leading dims flatten to >= rows."""
     h = h.contiguous()
     rows, R = h.shape
-    A = values.shape[-2] if values.shape[-1] == 1 else values.shape[-1]
-    rc = lib().atr_heads_values(_p(h), _p(critic.weight), _p(critic.bias), _p(values), rows, R, A, off, _stream(h))
-    if rc != 0:
-        raise RuntimeError("atr_heads_values failed (%d)" % rc)
+    A = _col_stride(values)
+    lib().atr_heads_values(_p(h), _p(critic.weight), _p(critic.bias), _p(values), rows, R, A, off, _stream(h))
 
 
 @torch.no_grad()
@@ -1240,11 +1188,9 @@ def heads_values2(hs, critics, values):
     h0, h1 = hs[0].contiguous(), hs[1].contiguous()
     rows, R = h0.shape
     assert h1.shape == h0.shape
-    A = values.shape[-2] if values.shape[-1] == 1 else values.shape[-1]
-    rc = lib().atr_heads_values2(_p(h0), _p(critics[0].weight), _p(critics[0].bias), 0, _p(h1), _p(critics[1].weight),
-                                 _p(critics[1].bias), 1, _p(values), rows, R, A, _stream(h0))
-    if rc != 0:
-        raise RuntimeError("atr_heads_values2 failed (%d)" % rc)
+    A = _col_stride(values)
+    lib().atr_heads_values2(_p(h0), _p(critics[0].weight), _p(critics[0].bias), 0, _p(h1), _p(critics[1].weight),
+                            _p(critics[1].bias), 1, _p(values), rows, R, A, _stream(h0))
 
 
 def _act_layout(actions, rows):
@@ -1254,6 +1200,14 @@ def _act_layout(actions, rows):
         return actions, actions.shape[1], actions.stride(0)
     a = actions.reshape(rows).contiguous()
     return a, rows, 0
+
+
+def _head_grads(dh, gs, A, R, has_aux):
+    """[dh, dWa, dba, dWc, dbc, dWaux, dbaux] of one player from the kernel's grads_and_sums record (include/atr_policy.h)."""
+    o = (A + 2) * R
+    dwa, dwc, dwx = gs[:A * R].view(A, R), gs[A * R:(A + 1) * R].view(1, R), gs[(A + 1) * R:o].view(1, R)
+    dba, dbc, dbx = gs[o:o + A], gs[o + A:o + A + 1], gs[o + A + 1:o + A + 2]
+    return [dh, dwa, dba, dwc, dbc, dwx if has_aux else None, dbx if has_aux else None]
 
 
 class _HeadsLossPair(torch.autograd.Function):
@@ -1282,11 +1236,11 @@ class _HeadsLossPair(torch.autograd.Function):
             a = arr[p]
             a.h, a.actions, a.act_n, a.act_tstride = h.data_ptr(), acts.data_ptr(), act_n, act_ts
             a.ret, a.gae, a.val = ret.data_ptr(), c["gae"].data_ptr(), c["val"].data_ptr()
-            a.stride = ret.shape[-2] if ret.shape[-1] == 1 else ret.shape[-1]
+            a.stride = _col_stride(ret)
             a.off = c["off"]
             r_aux = c.get("r_aux")
             a.r_aux = r_aux.data_ptr() if r_aux is not None else None
-            a.aux_stride = (r_aux.shape[-2] if r_aux.shape[-1] == 1 else r_aux.shape[-1]) if r_aux is not None else 0
+            a.aux_stride = _col_stride(r_aux) if r_aux is not None else 0
             a.aux_off = c.get("aux_off", 0)
             a.wa, a.ba, a.wc = wa.data_ptr(), ba.data_ptr(), wc.data_ptr()
             a.waux = waux.data_ptr() if waux is not None else None
@@ -1298,9 +1252,7 @@ class _HeadsLossPair(torch.autograd.Function):
             keep += [h, acts, ws]
         stats = torch.empty((2, 4), dtype=torch.float32, device=hs[0][0].device)
         arr[0].stats_out, arr[1].stats_out = stats.data_ptr(), stats.data_ptr() + 16
-        rc = L.atr_heads_loss_multi(arr, 2, float(cfg[0]["stats_scale"]), _stream(hs[0][0]))
-        if rc != 0:
-            raise RuntimeError("atr_heads_loss_multi failed (%d)" % rc)
+        L.atr_heads_loss_multi(arr, 2, float(cfg[0]["stats_scale"]), _stream(hs[0][0]))
         ctx.save_for_backward(hs[0][0], hs[0][1], hs[1][0], hs[1][1])
         ctx.dims = [(x[2], x[3], x[4]) for x in hs]
         ctx.set_materialize_grads(False)
@@ -1312,15 +1264,10 @@ class _HeadsLossPair(torch.autograd.Function):
         sv = ctx.saved_tensors
         out = [None]
         for p in range(2):
-            dh, gs = sv[2 * p], sv[2 * p + 1]
-            A, R, has_aux = ctx.dims[p]
             if (g0, g1)[p] is None:                 # this player's term is not part of the differentiated objective
                 out += [None] * 7
-                continue
-            o = (A + 2) * R
-            dwa, dwc, dwx = gs[:A * R].view(A, R), gs[A * R:(A + 1) * R].view(1, R), gs[(A + 1) * R:o].view(1, R)
-            dba, dbc, dbx = gs[o:o + A], gs[o + A:o + A + 1], gs[o + A + 1:o + A + 2]
-            out += [dh, dwa, dba, dwc, dbc, dwx if has_aux else None, dbx if has_aux else None]
+            else:
+                out += _head_grads(sv[2 * p], sv[2 * p + 1], *ctx.dims[p])
         return tuple(out)
 
 
@@ -1347,20 +1294,16 @@ class _HeadsLoss(torch.autograd.Function):
         h = h.contiguous()
         rows, R = h.shape
         A = wa.shape[0]
-        stride = ret.shape[-2] if ret.shape[-1] == 1 else ret.shape[-1]
+        stride = _col_stride(ret)
         rec = (A + 2) * R + (A + 2) + 4
         dh = torch.empty_like(h)
         gs = torch.empty(rec + 1, dtype=torch.float32, device=h.device)
         ws = torch.empty(L.atr_heads_workspace_floats(rows, R, A), dtype=torch.float32, device=h.device)
         actions = actions.contiguous()
-        aux_stride = 0
-        if r_aux is not None:
-            aux_stride = r_aux.shape[-2] if r_aux.shape[-1] == 1 else r_aux.shape[-1]
-        rc = L.atr_heads_loss(_p(h), _p(actions), _p(ret), _p(gae), _p(val), stride, off, _pn(r_aux), aux_stride, aux_off,
-                              _p(wa), _p(ba), _p(wc), _pn(waux), _pn(baux), float(scale), float(scale_aux), float(w_ent),
-                              _p(dh), _p(gs), _p(ws), rows, R, A, _stream(h))
-        if rc != 0:
-            raise RuntimeError("atr_heads_loss failed (%d)" % rc)
+        aux_stride = _col_stride(r_aux) if r_aux is not None else 0
+        L.atr_heads_loss(_p(h), _p(actions), _p(ret), _p(gae), _p(val), stride, off, _pn(r_aux), aux_stride, aux_off,
+                         _p(wa), _p(ba), _p(wc), _pn(waux), _pn(baux), float(scale), float(scale_aux), float(w_ent),
+                         _p(dh), _p(gs), _p(ws), rows, R, A, _stream(h))
         ctx.save_for_backward(dh, gs)
         ctx.dims = (A, R, waux is not None)
         ctx.unit_coeff = bool(unit_coeff)
@@ -1371,13 +1314,9 @@ class _HeadsLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gloss, gstats):
         dh, gs = ctx.saved_tensors
-        A, R, has_aux = ctx.dims
-        o = (A + 2) * R
         if not ctx.unit_coeff:          # the kernel's gradients are those of coefficient 1: apply the incoming one
             dh, gs = dh * gloss, gs * gloss
-        dwa, dwc, dwx = gs[:A * R].view(A, R), gs[A * R:(A + 1) * R].view(1, R), gs[(A + 1) * R:o].view(1, R)
-        dba, dbc, dbx = gs[o:o + A], gs[o + A:o + A + 1], gs[o + A + 1:o + A + 2]
-        return (dh, dwa, dba, dwc, dbc, dwx if has_aux else None, dbx if has_aux else None) + (None,) * 11
+        return tuple(_head_grads(dh, gs, *ctx.dims)) + (None,) * 11
 
 
 def heads_loss(h, actor, critic, aux, actions, ret, gae, val, off, r_aux, aux_off, scale, scale_aux, w_ent,
@@ -1405,10 +1344,8 @@ class _EmbedAdd(torch.autograd.Function):
         wc, bc = w.contiguous(), b.contiguous()
         out = torch.empty((rows, Cc), dtype=f.dtype, device=f.device)
         acts, act_n, act_ts = _act_layout(actions, rows)
-        rc = lib().atr_embed_add_ld(_p(f), f.stride(0), _p(wc), _p(bc), _p(acts), 1, act_n, act_ts, _p(out), rows, Cc, A,
-                                    _stream(f))
-        if rc != 0:
-            raise RuntimeError("atr_embed_add failed (%d)" % rc)
+        lib().atr_embed_add_ld(_p(f), f.stride(0), _p(wc), _p(bc), _p(acts), 1, act_n, act_ts, _p(out), rows, Cc, A,
+                               _stream(f))
         ctx.save_for_backward(acts)
         ctx.dims = (Cc, A, act_n, act_ts)
         return out
@@ -1423,9 +1360,7 @@ class _EmbedAdd(torch.autograd.Function):
         ws = torch.empty(L.atr_embed_grad_workspace_floats(rows, Cc, A), dtype=torch.float32, device=dout.device)
         dw = torch.empty((Cc, A), dtype=torch.float32, device=dout.device)
         db = torch.empty(Cc, dtype=torch.float32, device=dout.device)
-        rc = L.atr_embed_grad(_p(dout), _p(acts), 1, act_n, act_ts, _p(dw), _p(db), _p(ws), rows, Cc, A, _stream(dout))
-        if rc != 0:
-            raise RuntimeError("atr_embed_grad failed (%d)" % rc)
+        L.atr_embed_grad(_p(dout), _p(acts), 1, act_n, act_ts, _p(dw), _p(db), _p(ws), rows, Cc, A, _stream(dout))
         return dout, dw, db, None
 
 
@@ -1508,9 +1443,7 @@ class DeferredWeightGrads(object):
         L = lib()
         x0 = self.problems[0][0]
         ws = torch.empty(L.atr_gemm_tn_grouped_workspace_floats(arr, n, self.K), dtype=torch.float32, device=x0.device)
-        rc = L.atr_gemm_tn_grouped(arr, n, self.K, _p(ws), _stream(x0))
-        if rc != 0:
-            raise RuntimeError("atr_gemm_tn_grouped failed (%d)" % rc)
+        L.atr_gemm_tn_grouped(arr, n, self.K, _p(ws), _stream(x0))
         self.problems, self.K = [], None
         for fn in self.after:
             fn()
@@ -1568,22 +1501,12 @@ def gemm_tn(x1, x2, row_scale=None, colsum=False):
         c = torch.empty((M, N), dtype=torch.float32, device=x1.device)
         cs = torch.empty(M, dtype=torch.float32, device=x1.device) if colsum else None
         rs = row_scale.contiguous() if row_scale is not None else None
-        rc = L.atr_gemm_tn(_p(x1), _p(x2), _p(c), _p(ws), K, M, N, _pn(rs), _pn(cs), _stream(x1))
-        if rc != 0:
-            raise RuntimeError("atr_gemm_tn failed (%d)" % rc)
+        L.atr_gemm_tn(_p(x1), _p(x2), _p(c), _p(ws), K, M, N, _pn(rs), _pn(cs), _stream(x1))
         return (c, cs) if colsum else c
     if row_scale is not None:
         x1 = x1 * row_scale.unsqueeze(1)
     c = x1.t() @ x2
     return (c, x1.sum(0)) if colsum else c
-
-
-class RolloutConsts(C.Structure):
-    """atr_rollout_consts of include/atr_policy.h."""
-    _fields_ = [("w_ih", C.c_void_p * 2), ("w_hh", C.c_void_p * 2), ("b_ih", C.c_void_p * 2), ("b_hh", C.c_void_p * 2),
-                ("bsum", C.c_void_p), ("w_cat", C.c_void_p), ("fa_w", C.c_void_p), ("fa_b", C.c_void_p), ("emb_ih", C.c_void_p),
-                ("counter", C.c_void_p), ("fh0", C.c_void_p), ("fh_pstride", C.c_longlong), ("fh_ld", C.c_longlong),
-                ("F", C.c_int), ("A_act", C.c_int)]
 
 
 def rollout_consts_ok(consts):
@@ -1610,10 +1533,8 @@ def rollout_begin(hxs, cxs, h_all, c_all, obs_src=None, obs_dst=None, consts=Non
         nbytes = obs_src.numel() * obs_src.element_size()
         assert nbytes == obs_dst.numel() * obs_dst.element_size() and nbytes % 4 == 0
     if consts is None:
-        rc = lib().atr_rollout_begin(_p(hxs), _p(cxs), _p(h_all), _p(c_all), h_all.stride(0), _pn(obs_src), _pn(obs_dst), nbytes,
-                                     N, A, R, _stream(hxs))
-        if rc != 0:
-            raise RuntimeError("atr_rollout_begin failed (%d)" % rc)
+        lib().atr_rollout_begin(_p(hxs), _p(cxs), _p(h_all), _p(c_all), h_all.stride(0), _pn(obs_src), _pn(obs_dst), nbytes,
+                                N, A, R, _stream(hxs))
         return
     k = RolloutConsts()
     for p, l in enumerate(consts["lstm"]):
@@ -1630,14 +1551,8 @@ def rollout_begin(hxs, cxs, h_all, c_all, obs_src=None, obs_dst=None, consts=Non
         k.fa_w, k.fa_b, k.emb_ih, k.A_act = fa.weight.data_ptr(), fa.bias.data_ptr(), consts["emb_ih"].data_ptr(), fa.weight.shape[1]
     if counter is not None:
         k.counter = counter.data_ptr()
-    L = lib()
-    L.atr_rollout_begin2.restype = C.c_int
-    L.atr_rollout_begin2.argtypes = [C.c_void_p] * 4 + [C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int,
-                                                        C.c_int, C.POINTER(RolloutConsts), C.c_void_p]
-    rc = L.atr_rollout_begin2(_p(hxs), _p(cxs), _p(h_all), _p(c_all), h_all.stride(0), _pn(obs_src), _pn(obs_dst), nbytes,
+    lib().atr_rollout_begin2(_p(hxs), _p(cxs), _p(h_all), _p(c_all), h_all.stride(0), _pn(obs_src), _pn(obs_dst), nbytes,
                               N, A, R, C.byref(k), _stream(hxs))
-    if rc != 0:
-        raise RuntimeError("atr_rollout_begin2 failed (%d)" % rc)
 
 
 @torch.no_grad()
@@ -1657,10 +1572,8 @@ def rollout_end(h_all, c_all, dones, hxs, cxs, eps_len, keep, obs_src=None, obs_
         assert nbytes == obs_dst.numel() * obs_dst.element_size() and nbytes % 4 == 0
     if done_dst is not None:
         assert done_dst.dtype == torch.uint8 and done_dst.is_contiguous() and done_dst.numel() == N
-    rc = lib().atr_rollout_end2(_p(h_all[0, T]), _p(c_all[0, T]), h_all.stride(0), _p(dones), _p(hxs), _p(cxs), _p(eps_len),
-                                _p(keep), T, N, A, R, _pn(obs_src), _pn(obs_dst), nbytes, _pn(done_dst), _stream(hxs))
-    if rc != 0:
-        raise RuntimeError("atr_rollout_end failed (%d)" % rc)
+    lib().atr_rollout_end2(_p(h_all[0, T]), _p(c_all[0, T]), h_all.stride(0), _p(dones), _p(hxs), _p(cxs), _p(eps_len),
+                           _p(keep), T, N, A, R, _pn(obs_src), _pn(obs_dst), nbytes, _pn(done_dst), _stream(hxs))
 
 
 @torch.no_grad()
@@ -1668,17 +1581,13 @@ def adam_step(p, grad, exp_avg, exp_avg_sq, max_exp_avg_sq, scalars, step_size, 
               torch_eps=False):
     """SharedAdam.step over the flat bucket (csrc/driver_hip.hip): scalars = [step, beta1^step, beta2^step] float64;
     step_size: two floats of scratch. torch_eps: torch.optim.Adam's placement of eps and the bias corrections."""
-    rc = lib().atr_adam_step(_p(p), _p(grad), _p(exp_avg), _p(exp_avg_sq), _pn(max_exp_avg_sq), _p(scalars), _p(step_size),
-                             float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), 1 if torch_eps else 0,
-                             p.numel(), _stream(p))
-    if rc != 0:
-        raise RuntimeError("atr_adam_step failed (%d)" % rc)
+    lib().atr_adam_step(_p(p), _p(grad), _p(exp_avg), _p(exp_avg_sq), _pn(max_exp_avg_sq), _p(scalars), _p(step_size),
+                        float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), 1 if torch_eps else 0,
+                        p.numel(), _stream(p))
 
 
 @torch.no_grad()
 def rmsprop_step(p, grad, square_avg, lr, alpha, eps, weight_decay):
     """SharedRMSprop.step (momentum 0, not centered) over the flat bucket (csrc/driver_hip.hip)."""
-    rc = lib().atr_rmsprop_step(_p(p), _p(grad), _p(square_avg), float(lr), float(alpha), float(eps), float(weight_decay),
-                                p.numel(), _stream(p))
-    if rc != 0:
-        raise RuntimeError("atr_rmsprop_step failed (%d)" % rc)
+    lib().atr_rmsprop_step(_p(p), _p(grad), _p(square_avg), float(lr), float(alpha), float(eps), float(weight_decay),
+                           p.numel(), _stream(p))

@@ -83,10 +83,8 @@ class FlatParams(object):
                     else:
                         src[q] = None
                     dst[q], cnt[q] = off, numel
-                rc = L.atr_scatter_segments(src, dst, cnt, n, C.c_void_p(self.grad.data_ptr()),
-                                            C.c_void_p(torch.cuda.current_stream(self.grad.device).cuda_stream))
-                if rc != 0:
-                    raise RuntimeError("atr_scatter_segments failed (%d)" % rc)
+                L.atr_scatter_segments(src, dst, cnt, n, C.c_void_p(self.grad.data_ptr()),
+                                       C.c_void_p(torch.cuda.current_stream(self.grad.device).cuda_stream))
         else:
             assert not any(in_place)
             flat = []

@@ -1,5 +1,5 @@
 """CPU-side checks of the drop-in boundary: the C-ABI library loads without a GPU and exports every symbol that
-include/track2d.h declares; the env-id table equals the reference registry (golden registry.npz); the product
+include/track2d.h declares; the ctypes prototypes and structures of the policy kernels equal include/atr_policy.h; the env-id table equals the reference registry (golden registry.npz); the product
 path refuses to run without the GPU instead of falling back."""
 import ctypes
 import os
@@ -37,6 +37,127 @@ def test_library_exports_every_declared_symbol():
     assert len(atr_syms) >= 16 and "atr_stem_forward_u8" in atr_syms
     for s in np_syms + atr_syms:
         assert hasattr(lib, s), s
+
+
+_C_SCALARS = {"int": ctypes.c_int, "unsigned": ctypes.c_uint, "long long": ctypes.c_longlong,
+              "unsigned long long": ctypes.c_ulonglong, "float": ctypes.c_float, "double": ctypes.c_double}
+
+
+def _policy_header():
+    """include/atr_policy.h without comments and preprocessor lines."""
+    txt = open(os.path.join(ROOT, "include", "atr_policy.h")).read()
+    txt = re.sub(r"/\*.*?\*/", " ", txt, flags=re.S)
+    return "\n".join(ln for ln in re.sub(r"//[^\n]*", " ", txt).split("\n") if not ln.lstrip().startswith("#"))
+
+
+def _c_class(decl):
+    """The class of a C parameter / result / field type (the declared name already removed): "ptr" for any pointer, else the
+    ctypes scalar it must be bound as. An unknown type is a KeyError: the header uses nothing else."""
+    if "*" in decl:
+        return "ptr"
+    return _C_SCALARS[" ".join(w for w in decl.split() if w != "const")]
+
+
+def _py_class(t):
+    if t in (ctypes.c_void_p, ctypes.c_char_p) or (isinstance(t, type) and issubclass(t, ctypes._Pointer)):
+        return "ptr"
+    assert t in _C_SCALARS.values(), t
+    return t
+
+
+def _header_functions(txt):
+    """{name: (class of the result, [class per parameter])} of every atr_* function the header declares."""
+    out = {}
+    for m in re.finditer(r"([^;{}()]*?)\b(atr_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", txt):
+        params = [p.strip() for p in m.group(3).split(",")]
+        if params == ["void"]:
+            params = []
+        assert m.group(2) not in out
+        # (every parameter is named: what precedes the last identifier is its type)
+        out[m.group(2)] = (_c_class(m.group(1)), [_c_class(re.sub(r"\w+$", "", p)) for p in params])
+    return out
+
+
+def _header_structs(txt):
+    """{struct name: [(field, class, array length or None)]} of every typedef struct, multi-declarators expanded."""
+    out = {}
+    for m in re.finditer(r"typedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*(\w+)\s*;", txt, flags=re.S):
+        assert m.group(1) == m.group(3)
+        fields = []
+        for decl in (d.strip() for d in m.group(2).split(";")):
+            if not decl:
+                continue
+            first, *more = decl.split(",")
+            f = re.match(r"^([\w\s]+?)\s*(\**)\s*(\w+)\s*(?:\[(\d+)\])?$", first.strip())
+            assert f, decl
+            base = f.group(1)
+            decls = [f.groups()[1:]] + [re.match(r"^(\**)\s*(\w+)\s*(?:\[(\d+)\])?$", d.strip()).groups() for d in more]
+            for star, name, n in decls:
+                fields.append((name, _c_class(base + star), int(n) if n else None))
+        out[m.group(1)] = fields
+    return out
+
+
+def test_prototype_table_matches_the_policy_header():
+    """fused.ATR_PROTOTYPES is include/atr_policy.h's ABI: every declared function, with the header's parameter count and,
+    per parameter and result, the same class (pointer / int / unsigned / long long / unsigned long long / float / double).
+    ctypes converts silently, so a wrong entry would shift the kernel's argument list without any error."""
+    from active_tracking_rl_amd import fused
+    funcs = _header_functions(_policy_header())
+    assert sorted(funcs) == _header_symbols("atr_policy.h", "atr_") == sorted(fused.ATR_PROTOTYPES) and len(funcs) == 54
+    for name, (res, params) in funcs.items():
+        restype, argtypes = fused.ATR_PROTOTYPES[name][:2]
+        assert _py_class(restype) == res, name
+        assert len(argtypes) == len(params), name
+        for i, (a, c) in enumerate(zip(argtypes, params)):
+            assert _py_class(a) == c, (name, i)
+
+
+def test_structures_match_the_policy_header():
+    """Every typedef struct of include/atr_policy.h has its ctypes.Structure in fused.ATR_STRUCTS with the same field names,
+    order, array lengths and classes."""
+    from active_tracking_rl_amd import fused
+    structs = _header_structs(_policy_header())
+    assert sorted(structs) == sorted(fused.ATR_STRUCTS) and len(structs) == 8
+    for name, fields in structs.items():
+        got = []
+        for fname, t in fused.ATR_STRUCTS[name]._fields_:
+            arr = issubclass(t, ctypes.Array)
+            got.append((fname, _py_class(t._type_ if arr else t), t._length_ if arr else None))
+        assert got == fields, name
+
+
+def test_launch_status_is_checked_in_one_place():
+    """A status-returning entry point gets the table's errcheck: non-zero raises RuntimeError naming the entry point that
+    failed, 0 comes back as 0. The int results that are values (or that the caller handles) are the ones marked VALUE."""
+    from active_tracking_rl_amd import fused
+    for name in ("atr_embed_add_ld", "atr_rollout_end2", "atr_lstm_cell_forward_act1", "atr_lstm_bptt_pre2"):
+        check = fused._errcheck(name)
+        assert check(0, None, ()) == 0
+        with pytest.raises(RuntimeError, match=r"^%s failed \(-2\)$" % name):
+            check(-2, None, ())
+    unchecked = sorted(n for n, e in fused.ATR_PROTOTYPES.items() if e[0] is ctypes.c_int and fused.VALUE in e[2:])
+    assert unchecked == ["atr_gate_cell_workgroups", "atr_gemm_tn_set_corun", "atr_linear_kernel_name", "atr_linear_plan_info",
+                         "atr_linear_set_choice", "atr_lt_init", "atr_lt_library_info"]
+    assert all(e[0] is ctypes.c_int for e in fused.ATR_PROTOTYPES.values() if fused.VALUE in e[2:])
+    assert sorted(fused._ERROR_DETAIL) == ["atr_act_env_step", "atr_coop_env_step", "atr_linear"]
+
+
+def test_library_binding_applies_the_table():
+    """fused.lib() on the built library: every entry point carries the table's prototype, the checked ones the errcheck (with
+    the library's own error text where it keeps one), the VALUE ones none."""
+    from active_tracking_rl_amd import build, fused
+    build.build()
+    L = fused.lib()
+    for name, (restype, argtypes, *value) in fused.ATR_PROTOTYPES.items():
+        f = getattr(L, name)
+        assert f.restype is restype and list(f.argtypes or []) == list(argtypes), name
+        assert (f.errcheck is not None) == (restype is ctypes.c_int and not value), name
+    assert L.atr_gemm_tn.errcheck(0, None, ()) == 0
+    with pytest.raises(RuntimeError, match=r"^atr_linear failed \(-1\): "):
+        L.atr_linear.errcheck(-1, None, ())
+    with pytest.raises(RuntimeError, match=r"^atr_coop_env_step failed \(-3\): "):
+        L.atr_coop_env_step.errcheck(-3, None, ())
 
 
 def test_registry_matches_reference():
