@@ -18,6 +18,7 @@
 #include <new>
 #include <vector>
 
+#include "../../include/atr_eval.h"
 #include "../../include/atr_policy.h"
 #include "../../include/track2d.h"
 #include "../../include/track2d_np.h"
@@ -1611,8 +1612,9 @@ struct Step2 {
 
     // a_tr / a_tg: the two actions of this lane's env, already masked to the action table
     // returns the done flag of this lane's env (every lane of a slot computes it from the slot's replicated state)
+    // rw_out (nullable; the evaluation step's episode accounting): receives the step's reward pair in the env's leader lane
     __device__ __forceinline__ int finish(const DevState &s, int a_tr, int a_tg, int it, void *obs, float *rew,
-                                          uint8_t *done_out, uint32_t stamp)
+                                          uint8_t *done_out, uint32_t stamp, float2 *rw_out = nullptr)
     {
         const int side = (int)(cnt >> 24);
         int c_far = (int)(cnt & 0xffu), t = (int)((cnt >> 8) & 0xffffu);
@@ -1745,6 +1747,7 @@ struct Step2 {
             const float2 rwd = wall_tr ? (wall_tg ? rw_ss : rw_sm) : (wall_tg ? rw_ms : rw_mm);
             reinterpret_cast<float2 *>(rew)[(size_t)it * s.n + e] = rwd;
             done_out[(size_t)it * s.n + e] = (uint8_t)dn;
+            if (rw_out) *rw_out = rwd;
         }
         const bool consume = live && dn != 0 && s.auto_reset != 0;
 
@@ -1932,12 +1935,18 @@ __global__ __launch_bounds__(64 * kStep2Waves) void k_step2(DevState s, const vo
 // waves (STAGE_EMB: the embedding rows are parked in LDS here, behind a workgroup barrier every wave reaches), k_coop_step from a
 // workgroup whose earlier phases already staged them (STAGE_EMB = false: no barrier inside, waves without an env pair simply
 // do not call). tid / nthreads: the caller's thread index and workgroup size (the staging loop's shape).
-template <int OBS, bool RAM, bool ENV, int NA, bool NAV, bool STAGE_EMB, int NTHREADS>
+// GREEDY (the evaluation step, atr_eval_act_env_step; ENV only): the action is the first maximal logit instead of the Philox
+// draw — same logits, same lane, *a.counter is not read — and the env's leader lane keeps the evaluator's episode accounts
+// (ev_rsum f32 [N,2], ev_len i32 [N], ev_alive u8 [N]) with the step's reward and done flag still in its registers: plain
+// per-lane loads and stores of its own env's slots, no cross-lane traffic, no barrier. GREEDY = false is the code as it was.
+template <int OBS, bool RAM, bool ENV, int NA, bool NAV, bool STAGE_EMB, int NTHREADS, bool GREEDY = false>
 __device__ __forceinline__ void act_pair(const DevState &s, const atr_act_step &a, void *obs, float *rew, uint8_t *done_out,
                                          uint32_t stamp, int e0, int lane, int tid, uint32_t *stage, uint32_t *navtile,
-                                         float *emb_lds)
+                                         float *emb_lds, float *ev_rsum = nullptr, int *ev_len = nullptr,
+                                         uint8_t *ev_alive = nullptr)
 {
     using namespace atr;
+    static_assert(!GREEDY || ENV, "the evaluation step always steps the env");
     const int n = ENV ? s.n : a.N;
     // the embedding rows (A x 4R floats, 8 KB) go to LDS now: the target's cell reads row a_tracker the moment the tracker's
     // draw is known — an LDS read instead of a dependent trip to L2 in the middle of the kernel's serial chain
@@ -1988,7 +1997,18 @@ __device__ __forceinline__ void act_pair(const DevState &s, const atr_act_step &
         }
         cp[p] = ld4(a.c_prev[p] + (size_t)e * R + j);
     }
-    const unsigned long long ctr = *a.counter;
+    unsigned long long ctr = 0ull;
+    if (!GREEDY) ctr = *a.counter;
+    // evaluation: this env's accounts, fetched beside the policy's loads (only the leader lane of a live slot uses them)
+    float2 ev_rs = make_float2(0.f, 0.f);
+    int ev_ln = 0;
+    uint32_t ev_al = 0u;
+    const bool ev_lane = GREEDY && live && (lane & 31) == 15;     // Step2's leader: slot sl, agent 0, k = 15
+    if (ev_lane) {
+        ev_rs = reinterpret_cast<const float2 *>(ev_rsum)[e];
+        ev_ln = ev_len[e];
+        ev_al = ev_alive[e];
+    }
     if (STAGE_EMB) {
         if (a.emb) {
 #pragma unroll
@@ -2042,13 +2062,26 @@ __device__ __forceinline__ void act_pair(const DevState &s, const atr_act_step &
 #pragma unroll
             for (int x = 0; x < NA; x++) logit[x] = logit[x] + a.actor_b[p][x];
             // row index e and ordinal + p: the numbers atr_lstm_cell_forward_act* draw for this row
-            mine = draw_action(logit, NA, e, ctr, a.seed, a.ordinal + (unsigned)p);
+            if (GREEDY) {           // prob.max(1)[1] (model.py:45-46 of the reference) on the logits: the lowest maximal index
+#pragma unroll
+                for (int x = 1; x < NA; x++)
+                    if (logit[x] > logit[mine]) mine = x;
+            } else {
+                mine = draw_action(logit, NA, e, ctr, a.seed, a.ordinal + (unsigned)p);
+            }
             if (live) a.actions_out[(size_t)p * n + e] = (long long)mine;
         }
         act[p] = __shfl(mine, lane & 32, 64);
     }
     if (ENV) {
-        const int dn = S.finish(s, act[0] & s.amask, act[1] & s.amask, 0, obs, rew, done_out, stamp);
+        float2 ev_rw = make_float2(0.f, 0.f);
+        const int dn = S.finish(s, act[0] & s.amask, act[1] & s.amask, 0, obs, rew, done_out, stamp, GREEDY ? &ev_rw : nullptr);
+        if (ev_lane) {      // rsum += alive ? rew : 0 (f32, step order); length += alive; alive &= !done
+            const bool al = ev_al != 0u;
+            reinterpret_cast<float2 *>(ev_rsum)[e] = make_float2(ev_rs.x + (al ? ev_rw.x : 0.0f), ev_rs.y + (al ? ev_rw.y : 0.0f));
+            ev_len[e] = ev_ln + (al ? 1 : 0);
+            ev_alive[e] = (uint8_t)(al && dn == 0 ? 1 : 0);
+        }
         // the hidden rows as the NEXT step's LSTMCell GEMM reads them: zero for an env whose episode just ended (the reset() of
         // train.py:73-74 -> player_util.py:98-102), written into the h columns of that step's [features | k h] rows
         if (a.hm_out[0] && live) {
@@ -2073,6 +2106,23 @@ __global__ __launch_bounds__(64 * kStep2Waves) void k_act_step(DevState s, atr_a
     const int e0 = ((int)blockIdx.x * kStep2Waves + wave) * 2;
     act_pair<OBS, RAM, ENV, NA, NAV, true, 64 * kStep2Waves>(s, a, obs, rew, done_out, stamp, e0, lane, (int)threadIdx.x, stage2[wave],
                                                              navtiles[NAV ? wave : 0], emb_lds);
+}
+
+// k_act_step's evaluation form (atr_eval_act_env_step): the GREEDY instantiation of act_pair — argmax actions and the
+// evaluator's episode accounting in the same launch.
+template <int OBS, bool RAM, int NA, bool NAV>
+__global__ __launch_bounds__(64 * kStep2Waves) void k_eval_step(DevState s, atr_act_step a, atr_eval_out ev, void *obs, float *rew,
+                                                                uint8_t *done_out, uint32_t stamp)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t stage2[kStep2Waves][kStage2Words];
+    __shared__ __attribute__((aligned(16))) float emb_lds[NA * 4 * 128];
+    __shared__ __attribute__((aligned(16))) uint32_t navtiles[NAV ? kStep2Waves : 1][NAV ? kTileWords : 4];
+    const int lane = (int)(threadIdx.x & 63u);
+    const int wave = uni((int)(threadIdx.x >> 6));
+    const int e0 = ((int)blockIdx.x * kStep2Waves + wave) * 2;
+    act_pair<OBS, RAM, true, NA, NAV, true, 64 * kStep2Waves, true>(s, a, obs, rew, done_out, stamp, e0, lane, (int)threadIdx.x,
+                                                                    stage2[wave], navtiles[NAV ? wave : 0], emb_lds, ev.rsum,
+                                                                    ev.length, ev.alive);
 }
 
 // ---- the small-shard rollout step as ONE launch after the stem: fc + ReLU -> LSTMCell GEMM -> cells + heads + draws + env step ----
@@ -2918,25 +2968,27 @@ extern "C" int t2d_step_u8(t2d_handle *h, const void *act_tracker_dev, const voi
 
 // The rollout step's last launch (see k_act_step): policy cells + draws + env step. Same stamping / generator schedule
 // as t2d_step.
-extern "C" int atr_act_env_step(t2d_handle *h, const atr_act_step *args, void *obs_dev, int obs_is_u8, float *rew_dev,
-                                uint8_t *done_dev, void *stream)
+// ev != NULL: the evaluation form (atr_eval_act_env_step: greedy actions + episode accounting, k_eval_step); fn names the entry
+// point in the error text.
+static int act_env_step_impl(t2d_handle *h, const atr_act_step *args, const atr_eval_out *ev, void *obs_dev, int obs_is_u8,
+                             float *rew_dev, uint8_t *done_dev, void *stream, const char *fn)
 {
-    if (!args) return fail(T2D_ERR_INVALID, "atr_act_env_step: null argument");
+    if (!args) return fail(T2D_ERR_INVALID, "%s: null argument", fn);
     const atr_act_step &a = *args;
     for (int p = 0; p < 2; p++)
         if ((!a.ig[p] && p != 0) || !a.h_out[p] || !a.actor_w[p] || !a.actor_b[p] || (a.ig[p] && (!a.c_prev[p] || !a.c_out[p])))
-            return fail(T2D_ERR_INVALID, "atr_act_env_step: null policy buffer (player %d)", p);
+            return fail(T2D_ERR_INVALID, "%s: null policy buffer (player %d)", fn, p);
     if (!a.ig[0] && (a.hg[0] || a.acts[0]))
-        return fail(T2D_ERR_INVALID, "atr_act_env_step: ig[0] == NULL (the tracker's cell ran in atr_gate_cell) excludes hg[0] / acts[0]");
-    if (!a.actions_out || !a.counter || a.R != 128 || (a.A != 4 && a.A != 8))
-        return fail(T2D_ERR_INVALID, "atr_act_env_step: needs R = 128, A = 4 or 8, actions_out, counter");
+        return fail(T2D_ERR_INVALID, "%s: ig[0] == NULL (the tracker's cell ran in atr_gate_cell) excludes hg[0] / acts[0]", fn);
+    if (!a.actions_out || (!a.counter && !ev) || a.R != 128 || (a.A != 4 && a.A != 8))
+        return fail(T2D_ERR_INVALID, "%s: needs R = 128, A = 4 or 8, actions_out, counter", fn);
     if ((a.hm_out[0] != nullptr) != (a.hm_out[1] != nullptr) || (a.hm_out[0] && (a.hm_ld < a.R || (a.hm_ld & 3) ||
                                                                                  (((uintptr_t)a.hm_out[0] | (uintptr_t)a.hm_out[1]) & 15u))))
-        return fail(T2D_ERR_INVALID, "atr_act_env_step: hm_out needs both players, 16-byte aligned, hm_ld >= R and a multiple of 4");
-    if (a.hm_out[0] && !h) return fail(T2D_ERR_INVALID, "atr_act_env_step: hm_out (masked hidden rows) needs the env step");
+        return fail(T2D_ERR_INVALID, "%s: hm_out needs both players, 16-byte aligned, hm_ld >= R and a multiple of 4", fn);
+    if (a.hm_out[0] && !h) return fail(T2D_ERR_INVALID, "%s: hm_out (masked hidden rows) needs the env step", fn);
     hipStream_t st = (hipStream_t)stream;
     if (!h) {   // policy half only (the learner's bootstrap step: one more actor step, no env step)
-        if (a.N <= 0) return fail(T2D_ERR_INVALID, "atr_act_env_step: N must be > 0 without an env handle");
+        if (a.N <= 0) return fail(T2D_ERR_INVALID, "%s: N must be > 0 without an env handle", fn);
         DevState none;
         std::memset(&none, 0, sizeof(none));
         const unsigned grid = (unsigned)(((a.N + 1) / 2 + kStep2Waves - 1) / kStep2Waves);
@@ -2949,17 +3001,17 @@ extern "C" int atr_act_env_step(t2d_handle *h, const atr_act_step *args, void *o
         HIP_TRY(hipGetLastError());
         return T2D_OK;
     }
-    if (!rew_dev || !done_dev || !obs_dev) return fail(T2D_ERR_INVALID, "atr_act_env_step: null env buffer");
+    if (!rew_dev || !done_dev || !obs_dev) return fail(T2D_ERR_INVALID, "%s: null env buffer", fn);
     if (h->np_inter)
-        return fail(T2D_ERR_INVALID, "atr_act_env_step: numpy-stream Ram handles take the target's action from k_ram_np before the "
-                                     "step launch (t2d_step / t2d_step_u8), not from the policy's draw inside this kernel");
+        return fail(T2D_ERR_INVALID, "%s: numpy-stream Ram handles take the target's action from k_ram_np before the "
+                                     "step launch (t2d_step / t2d_step_u8), not from the policy's draw inside this kernel", fn);
     if (!use_step2(h))
-        return fail(T2D_ERR_INVALID, "atr_act_env_step: exists for 'Partial' ids without the RPF target (the k_step2 family)");
-    if (a.N != h->s.n) return fail(T2D_ERR_INVALID, "atr_act_env_step: policy batch %d != %d envs", a.N, h->s.n);
-    if (a.A != h->s.amask + 1) return fail(T2D_ERR_INVALID, "atr_act_env_step: %d policy actions, env has %d", a.A, h->s.amask + 1);
-    if (obs_is_u8 && ((uintptr_t)obs_dev & 3u) != 0u) return fail(T2D_ERR_INVALID, "atr_act_env_step: obs buffer must be 4-byte aligned");
-    if (!h->reset_done) return fail(T2D_ERR_STATE, "atr_act_env_step: call t2d_reset (all envs) or t2d_inject first");
-    if (h->s.auto_reset && !h->primed) return fail(T2D_ERR_STATE, "atr_act_env_step: auto_reset needs one t2d_reset before stepping");
+        return fail(T2D_ERR_INVALID, "%s: exists for 'Partial' ids without the RPF target (the k_step2 family)", fn);
+    if (a.N != h->s.n) return fail(T2D_ERR_INVALID, "%s: policy batch %d != %d envs", fn, a.N, h->s.n);
+    if (a.A != h->s.amask + 1) return fail(T2D_ERR_INVALID, "%s: %d policy actions, env has %d", fn, a.A, h->s.amask + 1);
+    if (obs_is_u8 && ((uintptr_t)obs_dev & 3u) != 0u) return fail(T2D_ERR_INVALID, "%s: obs buffer must be 4-byte aligned", fn);
+    if (!h->reset_done) return fail(T2D_ERR_STATE, "%s: call t2d_reset (all envs) or t2d_inject first", fn);
+    if (h->s.auto_reset && !h->primed) return fail(T2D_ERR_STATE, "%s: auto_reset needs one t2d_reset before stepping", fn);
     DeviceGuard guard(h->device);
     if (h->s.auto_reset) {
         int rc = window_begin(h, st);
@@ -2968,8 +3020,14 @@ extern "C" int atr_act_env_step(t2d_handle *h, const atr_act_step *args, void *o
     }
     const int kind = obs_is_u8 ? OBS_U8 : ((((uintptr_t)obs_dev & 15u) == 0u) ? OBS_F32_VEC4 : OBS_F32_SCALAR);
 #define T2D_LAUNCH_ACT2(KIND, RAMV, NAV, NAVF)                                                                          \
-    hipLaunchKernelGGL((k_act_step<KIND, RAMV, true, NAV, NAVF>), pair_grid(h->s.n), dim3(64 * kStep2Waves), 0, st, h->s, a, \
-                       obs_dev, rew_dev, done_dev, h->phase)
+    do {                                                                                                               \
+        if (ev)                                                                                                        \
+            hipLaunchKernelGGL((k_eval_step<KIND, RAMV, NAV, NAVF>), pair_grid(h->s.n), dim3(64 * kStep2Waves), 0, st, h->s, a, \
+                               *ev, obs_dev, rew_dev, done_dev, h->phase);                                             \
+        else                                                                                                           \
+            hipLaunchKernelGGL((k_act_step<KIND, RAMV, true, NAV, NAVF>), pair_grid(h->s.n), dim3(64 * kStep2Waves), 0, st, h->s, a, \
+                               obs_dev, rew_dev, done_dev, h->phase);                                                  \
+    } while (0)
 #define T2D_LAUNCH_ACT(KIND)                                                                                           \
     do {                                                                                                               \
         if (h->has_navmode) { if (a.A == 4) T2D_LAUNCH_ACT2(KIND, true, 4, true); else T2D_LAUNCH_ACT2(KIND, true, 8, true); } \
@@ -2984,6 +3042,25 @@ extern "C" int atr_act_env_step(t2d_handle *h, const atr_act_step *args, void *o
     HIP_TRY(hipGetLastError());
     if (h->s.auto_reset) return window_end(h, st);
     return T2D_OK;
+}
+
+extern "C" int atr_act_env_step(t2d_handle *h, const atr_act_step *args, void *obs_dev, int obs_is_u8, float *rew_dev,
+                                uint8_t *done_dev, void *stream)
+{
+    return act_env_step_impl(h, args, nullptr, obs_dev, obs_is_u8, rew_dev, done_dev, stream, "atr_act_env_step");
+}
+
+// The evaluator's step (include/atr_eval.h): atr_act_env_step with the first-max action in place of the draw and the episode
+// accounting of test.evaluate in the same launch.
+extern "C" int atr_eval_act_env_step(t2d_handle *h, const atr_act_step *args, const atr_eval_out *out, void *obs_dev, int obs_is_u8,
+                                     float *rew_dev, uint8_t *done_dev, void *stream)
+{
+    if (!h) return fail(T2D_ERR_INVALID, "atr_eval_act_env_step: needs an env handle (the evaluation step always steps the env)");
+    if (!out || !out->rsum || !out->length || !out->alive)
+        return fail(T2D_ERR_INVALID, "atr_eval_act_env_step: null accounting buffer (rsum, length, alive)");
+    if (((uintptr_t)out->rsum & 7u) != 0u || ((uintptr_t)out->length & 3u) != 0u)
+        return fail(T2D_ERR_INVALID, "atr_eval_act_env_step: rsum must be 8-byte aligned, length 4-byte aligned");
+    return act_env_step_impl(h, args, out, obs_dev, obs_is_u8, rew_dev, done_dev, stream, "atr_eval_act_env_step");
 }
 
 // The small-shard rollout step after the stem as ONE launch (k_coop_step): fc + ReLU of both encoders, the LSTMCell GEMM of

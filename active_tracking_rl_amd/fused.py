@@ -1036,7 +1036,7 @@ def _env_out_args(env_out):
 
 @torch.no_grad()
 def act_env_step(env_core, ig, hg, biases, c_prev, done, h_out, c_out, acts, sampler, actors, actions_out, emb=None,
-                 env_out=None, hm_out=None):
+                 env_out=None, hm_out=None, greedy=False, eval_out=None):
     """The END of a rollout step as ONE launch (atr_act_env_step, csrc/track2d_hip.hip k_act_step): both players' cells +
     actor heads + draws (tracker first; emb [A,4R] adds emb[a_tracker] to the target's pre-activations) and, with
     env_core (a vec_env.VecTrack2D) and env_out = (obs [N,2,13,13] u8 | f32, rew [N,2], done [N] u8), the env step with
@@ -1044,9 +1044,18 @@ def act_env_step(env_core, ig, hg, biases, c_prev, done, h_out, c_out, acts, sam
     [4R] or None; c_prev / h_out / c_out per-player [N,R]; acts per-player [N,4R] or None; actions_out int64 [2,N].
     hm_out (with the env step only): per-player [N,R] views with a common row stride — they receive the fresh hidden rows
     zeroed where this step's done flag is set (what the next step's LSTMCell GEMM reads).
-    Same results as lstm_cell_act_into x 2 + env.step. Only valid inside sampler.begin_block(); consumes two ordinals."""
+    Same results as lstm_cell_act_into x 2 + env.step. Only valid inside sampler.begin_block(); consumes two ordinals.
+    greedy (with the env step only) + eval_out = (rsum f32 [N,2], length i32 [N], alive u8 [N]): the evaluation form
+    (atr_eval_act_env_step, include/atr_eval.h) — same cells, the first maximal logit instead of the draw, and the evaluator's
+    episode accounting in the same launch."""
     assert hm_out is None or env_core is not None
     a = _act_step_args(ig, hg, biases, c_prev, done, h_out, c_out, acts, sampler, actors, actions_out, emb, hm_out)
+    if greedy:
+        from . import evaluator
+        if env_core is None or eval_out is None:
+            raise RuntimeError("the greedy step exists with the env step and the evaluator's accounts only (atr_eval_act_env_step)")
+        evaluator.eval_act_env_step(env_core, a, eval_out, env_out, _stream(h_out[0]))
+        return actions_out
     if env_core is None:
         lib().atr_act_env_step(None, C.byref(a), None, 0, None, None, _stream(h_out[0]))
     else:

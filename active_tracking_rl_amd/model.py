@@ -742,11 +742,13 @@ class A3C_Dueling(nn.Module):
         cache.consts = None
 
     @torch.no_grad()
-    def act_cached(self, states, cache, t, done=None, env_out=None):
+    def act_cached(self, states, cache, t, done=None, env_out=None, greedy=None):
         """act() for step t of a cached rollout: same sampling and state update, every intermediate written into the
         cache's slot t (LSTM state of step t lives in cache.h_all/c_all[:, t], the new one goes to slot t+1).
         env_out = (vec_env.VecTrack2D, obs slot, reward slot, done slot): where the kernels allow it the env step runs
-        inside the step's last launch (fused.act_env_step); self.env_stepped tells the caller whether it did."""
+        inside the step's last launch (fused.act_env_step); self.env_stepped tells the caller whether it did.
+        greedy = (rsum, length, alive): the evaluator's step (evaluator.GreedyEvaluator) — argmax actions and its episode
+        accounts kept by that same launch; an error where the step would not end in it."""
         return self._act_step(states, cache, [cache.y[0][t], cache.y[1][t]], [cache.f[0][t], cache.f[1][t]],
                               cache.feat1[t] if cache.feat1 is not None else None,
                               cache.h_all[:, t], cache.c_all[:, t], cache.h_all[:, t + 1], cache.c_all[:, t + 1],
@@ -754,7 +756,7 @@ class A3C_Dueling(nn.Module):
                               cache.actions[t] if cache.actions is not None else None, done,
                               f_pair=cache.f_all[:, t] if cache.f_all is not None else None, env_out=env_out,
                               fh=(cache.fh_all[:, t], cache.fh_all[:, t + 1]) if cache.fh_all is not None else None,
-                              gates=cache.pre_all[:, t] if getattr(cache, "pre_all", None) is not None else None)
+                              gates=cache.pre_all[:, t] if getattr(cache, "pre_all", None) is not None else None, greedy=greedy)
 
     @torch.no_grad()
     def boot_values(self, states, cache, done, v_out):
@@ -784,7 +786,7 @@ class A3C_Dueling(nn.Module):
         return v_out
 
     def _act_step(self, states, cache, y, f_out, feat1, h_prev, c_prev, h_out, c_out, acts, actions, done, f_pair=None,
-                  env_out=None, fh=None, gates=None):
+                  env_out=None, fh=None, gates=None, greedy=None):
         """One actor step of both players on explicit buffers: y / f_out per-player stem and fc outputs, h_prev / c_prev
         [2,N,R] (un-masked; `done` [N] uint8 of the previous step is applied inside), h_out / c_out [2,N,R], acts
         [2,N,4R] (activated gates), actions [2,N] int64 or None."""
@@ -811,6 +813,9 @@ class A3C_Dueling(nn.Module):
                      and self._sampler._ordinal is not None and getattr(cache, "has_wih_t", False)
                      and all(t.is_contiguous() for t in (c_prev[0], c_prev[1], h_out[0], h_out[1], c_out[0], c_out[1],
                                                          h_prev[0], h_prev[1]) + ((acts[0], acts[1]) if acts is not None else ())))
+        if greedy is not None and not (env_fused and env_out is not None):
+            raise RuntimeError("the greedy evaluation step is the rollout's fused env step (k_act_step) or nothing: this step would "
+                               "take another branch (evaluator.supported tells beforehand)")
         if not env_fused and acts is None:
             raise RuntimeError("this rollout cache keeps the gate GEMM's output instead of the activated gates (store_preacts), "
                                "which only the one-GEMM step fills; the step at hand takes another branch")
@@ -825,7 +830,7 @@ class A3C_Dueling(nn.Module):
         # step itself as ONE launch (csrc/track2d_hip.hip k_act_step): stem, 2 x fc, 2 x bmm, act+env = 6 launches per step
         if env_fused:
             core = env_out[0] if env_out is not None else None
-            if (cat_gemm and env_out is not None and fh[1] is not None and p0.encoder.outdim == p1.encoder.outdim
+            if (cat_gemm and env_out is not None and fh[1] is not None and p0.encoder.outdim == p1.encoder.outdim and greedy is None
                     and self._coop_ok(n, p0.encoder.outdim, R, states.device)):
                 # small shards: fc pair -> LSTMCell GEMM -> cells + heads + draws + env step as ONE launch whose workgroups
                 # cooperate per XCD (csrc/track2d_hip.hip k_coop_step): stem + this = 2 launches per env step
@@ -894,7 +899,7 @@ class A3C_Dueling(nn.Module):
             fused.act_env_step(core, ig, hg_, bs, c_prev, done, h_out, c_out, acts, self._sampler,
                                (p0.actor.actor_linear, p1.actor.actor_linear), actions,
                                emb=cache.emb_ih if self.tat else None, env_out=env_out[1:] if env_out is not None else None,
-                               hm_out=hm)
+                               hm_out=hm, greedy=greedy is not None, eval_out=greedy)
             if hm is not None:            # slot t + 1 of the [features | k h] rows now holds k_t h_t (the learner's dW_hh reads
                 cache.hm_written = getattr(cache, "hm_written", 0) + 1        # them when every step of the rollout wrote one)
             self.env_stepped = env_out is not None

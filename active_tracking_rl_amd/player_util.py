@@ -40,6 +40,7 @@ class Agent(object):
         self.fused_bookkeeping = True   # rollout prologue / epilogue as one launch each (csrc/driver_hip.hip)
         self._keep = None
         self.carry_out, self.carry_written, self._want_loss_terms = None, (), False
+        self.greedy_eval = None     # (rsum, length, alive) of evaluator.GreedyEvaluator: action_rollout steps greedily
         self._one = torch.ones((), dtype=torch.float32, device=device)   # seed of the backward pass (made outside any capture)
         self.done = torch.ones(self.num_envs, dtype=torch.uint8, device=device)
         self.info = None
@@ -90,8 +91,14 @@ class Agent(object):
             if self._buf is not None and hasattr(self.env, "fused_step_out"):
                 t = len(self.states)
                 env_out = self.env.fused_step_out((self._buf[0][t + 1], self._buf[1][t], self._buf[2][t]))
-            actions = self.model.act_cached(self.state, self._cache, len(self.states), self._pending_done, env_out=env_out)
+            if self.greedy_eval is not None:
+                actions = self.model.act_cached(self.state, self._cache, len(self.states), self._pending_done, env_out=env_out,
+                                                greedy=self.greedy_eval)
+            else:
+                actions = self.model.act_cached(self.state, self._cache, len(self.states), self._pending_done, env_out=env_out)
             stepped = env_out is not None and getattr(self.model, "env_stepped", False)
+        elif self.greedy_eval is not None:
+            raise RuntimeError("greedy evaluation needs the cached rollout path (evaluator.supported tells beforehand)")
         elif hasattr(self.model, "act") and self.num_agents == 2 and not getattr(self.model, "single", False):
             actions, self._hs, self._cs = self.model.act(self.state, self._hs, self._cs, self._pending_done)
         else:

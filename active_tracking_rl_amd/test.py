@@ -23,9 +23,16 @@ from .utils import ScalarWriter, check_path, setup_logger
 
 
 @torch.no_grad()
-def evaluate(model, env_id, args, device, episodes, seed=None):
+def evaluate(model, env_id, args, device, episodes, seed=None, graphed=False):
     """Run `episodes` envs of `env_id` in parallel until each has finished ONE episode. Returns per-episode reward
-    sums [episodes, 2] and lengths [episodes] (numpy)."""
+    sums [episodes, 2] and lengths [episodes] (numpy). graphed: the round on the rollout's kernels as replayed hipGraphs
+    (evaluator.GreedyEvaluator) where they apply, else — with one warning line — the eager round below."""
+    if graphed:
+        from . import evaluator
+        try:
+            return evaluator.GreedyEvaluator(model, env_id, args, device, episodes).run()
+        except evaluator.Unsupported as ex:
+            logging.getLogger(__name__).warning("graphed evaluation falls back to the eager round: %s", ex)
     ev = create_env(env_id, args, num_envs=max(2, episodes), device=str(device),
                     env_id_base=getattr(args, "eval_env_id_base", 1 << 20))
     n = ev.num_envs
@@ -118,7 +125,8 @@ def test(args, shared_model, train_modes, n_iters, rounds=None, state=None):
     done_rounds = 0
     while rounds is None or done_rounds < rounds:
         t0 = time.time()
-        rsum, length = evaluate(shared_model, env_id, args, device, args.test_eps)
+        rsum, length = evaluate(shared_model, env_id, args, device, args.test_eps,
+                                graphed=bool(getattr(args, "graphed_eval", False)))
         n_iter = int(sum(n_iters))
         schedule_train_modes(args, train_modes, n_iter, state)                       # test.py:84-92
         # test.py:93-97: one record per evaluation episode at step n_iter. test/fps in the reference is the env steps per

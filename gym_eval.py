@@ -37,6 +37,9 @@ parser.add_argument('--single', dest='single', action='store_true', help='single
 parser.add_argument('--rescale', dest='rescale', action='store_true', help='rescale image to [-1, 1]')
 parser.add_argument('--rnn-out', type=int, default=128, metavar='LO', help='lstm output size')
 parser.add_argument('--aux', default='reward', help='auxiliary task: reward/none')
+parser.add_argument('--graphed-eval', dest='graphed_eval', action='store_true',
+                    help='run the episodes on the rollout kernels as replayed hipGraphs where the env allows it')
+parser.add_argument('--num-steps', type=int, default=20, metavar='NS', help='env steps per replayed graph (--graphed-eval)')
 
 if __name__ == '__main__':
     args = parser.parse_args()
@@ -64,7 +67,7 @@ if __name__ == '__main__':
     if args.load_target is not None:
         model.player1.load_state_dict(load(args.load_target))             # :88-92
     args.gpu_ids = [device.index]
-    rsum, length = evaluate(model, args.env, args, device, args.num_episodes)
+    rsum, length = evaluate(model, args.env, args, device, args.num_episodes, graphed=args.graphed_eval)
     reward_mean, reward_std = rsum.mean(0), rsum.std(0)
     len_mean, len_std = length.mean(), length.std()
     success_rate = float((length >= 500).mean())

@@ -59,6 +59,9 @@ parser.add_argument('--num-envs', type=int, default=4096, metavar='N', help='par
 parser.add_argument('--num-steps', type=int, default=20, metavar='NS', help='number of forward steps in A3C')
 parser.add_argument('--test-eps', type=int, default=100, metavar='TE', help='evaluation episodes per round')
 parser.add_argument('--test-every', type=int, default=200, metavar='TI', help='training iterations between evaluations')
+parser.add_argument('--graphed-eval', dest='graphed_eval', action='store_true',
+                    help='evaluation rounds on the rollout kernels as replayed hipGraphs (greedy step with on-device episode '
+                         'accounting) where the env allows it')
 parser.add_argument('--env', default='Track2D-BlockPartialPZR-v0', metavar='ENV', help='environment to train on')
 parser.add_argument('--env-base', default='Track2D-BlockPartialNav-v0', metavar='ENVB', help='environment to test on ')
 parser.add_argument('--optimizer', default='Adam', metavar='OPT', help='shares optimizer choice of Adam or RMSprop')
