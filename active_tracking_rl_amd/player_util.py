@@ -278,6 +278,9 @@ class Agent(object):
         self.eps_len = torch.zeros(self.num_envs, dtype=torch.int32, device=self.device)
         self.done = torch.zeros(self.num_envs, dtype=torch.uint8, device=self.device)
         self.reset_rnn_hiden()
+        stats = getattr(self.env, "episode_stats", None)      # (episode_stats.EpisodeStats: the episodes in flight are gone)
+        if stats is not None:
+            stats.reset_running()
 
     def clear_actions(self):
         self.values, self.log_probs, self.rewards, self.entropies, self.preds, self.dones = [], [], [], [], [], []

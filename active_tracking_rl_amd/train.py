@@ -87,6 +87,16 @@ def rollout(player, num_steps, fast=True):
         player.update_rnn_hiden()
         for _ in range(num_steps):
             player.action_train()
+    # training-episode statistics (episode_stats.EpisodeStats, opt-in: attached to the env SHARD, so whichever player or replica
+    # ran these steps continues the same accounts): one launch over the step rewards and done flags just stored, on the
+    # rollout's stream and inside its captured graph. Nothing attached: nothing is launched.
+    stats = getattr(player.env, "episode_stats", None)
+    if stats is not None:
+        buf = player._buf if fast else None
+        if buf is not None and buf[2].shape[0] == num_steps:
+            stats.update(buf[1], buf[2])
+        else:
+            stats.update(torch.stack(player.rewards[-num_steps:]), torch.stack(player.dones[-num_steps:]))
     # A rollout that is not a whole number of generator stamp cycles restarts the stamps (so that a captured rollout
     # replays consistently); otherwise forked generator launches stay in flight under the learner's kernels.
     if hasattr(player.env, "flush") and num_steps % getattr(player.env, "generator_cycle", 1) != 0:
@@ -786,6 +796,10 @@ def train(rank, args, shared_model, optimizer, train_modes, n_iters, env=None):
     player, optimizer = make_player(args, device, rank, world, env=env, model=shared_model, optimizer=optimizer)
     from .utils import ScalarWriter, log_train_scalars
     writer = ScalarWriter(os.path.join(args.log_dir, 'Agent:{}'.format(rank)))
+    ep_stats = None
+    if getattr(args, "episode_stats", False):       # (make_player has just reset the shard: every env is at step 0)
+        from .episode_stats import EpisodeStats
+        ep_stats = EpisodeStats(player.env, device)
     n_iter = 0
     try:
         while True:
@@ -801,6 +815,8 @@ def train(rank, args, shared_model, optimizer, train_modes, n_iters, env=None):
                 fps = args.num_steps * player.num_envs / (time.time() - t0)
                 log_train_scalars(writer, (policy_loss, value_loss, entropies, pred_loss), training_mode, fps, player.n_steps,
                                   player.num_agents)
+                if ep_stats is not None:
+                    ep_stats.record(writer, player.n_steps, rank)
                 writer.flush()
             if train_modes[rank] == -100 or n_iter * world > args.max_step:   # test.py:129-134 stop rule
                 break

@@ -101,6 +101,10 @@ parser.add_argument('--burn-in', type=int, default=150, metavar='BI',
                     help='iterations before training whose updates are discarded: the envs of a fresh shard all start an episode '
                          'at step 0 together, and the first updates would fit that one phase (0: start synchronised, as a single '
                          'reference worker does)')
+parser.add_argument('--episode-stats', dest='episode_stats', action='store_true',
+                    help='keep returns and lengths of the training episodes on the device (one more launch per rollout) and '
+                         'write train/reward_0, train/reward_1, train/eps_len, train/success_rate, train/episodes with every '
+                         '--log-every record')
 parser.add_argument('--adv-step', type=int, default=None, metavar='AS',
                     help="--train-mode 2 only: iterations the TARGET trains before the evaluator hands back to the tracker "
                          "(test.py:88-91 of the reference reads args.adv_step, which its own main.py never defines)")
@@ -137,6 +141,10 @@ if __name__ == '__main__':
         dist.barrier()
     args.log_dir = os.path.join(args.log_dir, args.env, datetime.now().strftime('%b%d_%H-%M'))
     player, optimizer = make_player(args, device, rank, world)
+    ep_stats = None
+    if args.episode_stats:      # attached to the fresh shard, before any schedule captures a rollout over it
+        from active_tracking_rl_amd.episode_stats import EpisodeStats
+        ep_stats = EpisodeStats(player.env, device)
     if args.load_model_dir is not None:
         saved_state = torch.load(args.load_model_dir, map_location=lambda storage, loc: storage)
         player.model.load_state_dict(saved_state)
@@ -166,6 +174,12 @@ if __name__ == '__main__':
     elif args.burn_in > 0 and rank == 0:
         print("warning: --burn-in %d ignored with --no-graph (the eager loop has no rollback of its updates)" % args.burn_in,
               file=sys.stderr, flush=True)
+    if ep_stats is not None and sched is not None:
+        # warm-up iterations, tune_streams trials and burn-in moved the shard on without being training: the episodes they
+        # finished are drained and dropped; the episodes in flight carry on and are counted whole when they end
+        sched.finish()
+        torch.cuda.synchronize(device)
+        ep_stats.drain()
     step = sched.run if sched is not None else None
     drain = getattr(sched, "finish", lambda: None)          # pipelined: both streams joined before the host reads anything
     it = 0
@@ -196,6 +210,8 @@ if __name__ == '__main__':
             now = time.time()
             fps = (it - it_log) * args.num_steps * player.num_envs / max(now - t_log, 1e-9)
             log_train_scalars(writer, stats, train_modes[rank], fps, it * args.num_steps * player.num_envs, player.num_agents)
+            if ep_stats is not None:    # drain, pool over ranks, summarise: episodes finished since the last record
+                ep_stats.record(writer, it * args.num_steps * player.num_envs, rank)
             writer.flush()
             t_log, it_log = time.time(), it
         if it % args.test_every == 0 or it > args.max_step:
