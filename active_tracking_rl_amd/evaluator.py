@@ -101,6 +101,8 @@ def supported(env, model):
         return False
     if getattr(model, "single", True) or not hasattr(model, "player1"):
         return False
+    if not getattr(model, "cacheable_core", True):       # (GRU cores: no cached rollout, hence no fused step)
+        return False
     buf = env.rollout_buffers(1)
     if buf is None or env.fused_step_out((buf[0][1], buf[1][0], buf[2][0])) is None:
         return False

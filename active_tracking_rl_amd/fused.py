@@ -8,6 +8,8 @@ every launch goes through it, so a launch status other than 0 raises RuntimeErro
   lstm_cell / lstm_cell_into / lstm_cell_act_into, lstm_sequence(_cached)
                                                 masked LSTMCell step(s), the actor's cell + head + draw in one launch,
                                                 the whole recurrence as one autograd node (csrc/lstm_hip.hip)
+  gru_cell, gru_sequence                        the GRU cores' masked GRUCell step and their whole recurrence as one autograd
+                                                node, on the path without a rollout cache (include/atr_gru.h, csrc/gru_hip.hip)
   ActionSampler                                 actor head + categorical draw (csrc/policy_hip.hip)
   gae_returns, heads_values, heads_loss         returns / GAE, critic values, heads + A3C loss terms with analytic
                                                 gradients (csrc/lstm_hip.hip, csrc/heads_hip.hip)
@@ -171,6 +173,16 @@ def _prototypes():
 
 
 ATR_PROTOTYPES = _prototypes()
+# the GRU core's header, include/atr_gru.h (held to it by tests/test_gru_cpu.py): bound and checked by lib() like the table above
+GRU_PROTOTYPES = {
+    "atr_gru_cell_forward": (C.c_int, [C.c_void_p] * 6 + [C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong,
+                                       C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "atr_gru_cell_backward": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong,
+                                        C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int,
+                                        C.c_void_p]),
+    "atr_gru_bptt": (C.c_int, [C.c_void_p] * 4 + [C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p,
+                               C.c_longlong, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+}
 # the library's own text for a failed launch, where it keeps one
 _ERROR_DETAIL = {"atr_act_env_step": "t2d_last_error", "atr_coop_env_step": "t2d_last_error", "atr_linear": "atr_lt_last_error"}
 
@@ -189,7 +201,7 @@ def lib():
     global _lib
     if _lib is None:
         L = vec_env.load_library()
-        for name, (restype, argtypes, *value) in ATR_PROTOTYPES.items():
+        for name, (restype, argtypes, *value) in list(ATR_PROTOTYPES.items()) + list(GRU_PROTOTYPES.items()):
             f = getattr(L, name)
             f.restype, f.argtypes = restype, argtypes
             if restype is C.c_int and not value:
@@ -785,6 +797,105 @@ def _lstm_bptt(whh, keep, h_all, c_all, acts, dhs, whh_nn=None, want_dwhh=True, 
         hm = (h_all[:, :T] * kprev.view(1, T, N, 1)).view(P, T * N, R)
         dwhh = torch.bmm(hm.transpose(1, 2), dG)
     return dG, dhn, dcc, dwhh
+
+
+def gru_cell(ig, hg, b_hh, h_prev, keep=None, done=None):
+    """One no-grad GRUCell step for the rollout (csrc/gru_hip.hip): ig [N,3R] = x W_ih^T + b_ih, hg [N,3R] = h_prev W_hh^T with
+    h_prev [N,R] NOT masked; the previous step's episode-boundary mask (keep [N] float, or done [N] uint8) is applied inside, to
+    the hidden product and to the z h term, and b_hh [3R] is added after it. Returns h [N,R]."""
+    N, R = h_prev.shape
+    h = torch.empty_like(h_prev)
+    lib().atr_gru_cell_forward(_p(ig), None, _p(hg), _p(b_hh), None, _p(h_prev), 0, _pn(keep), _pn(done), _p(h), 0, None, 0,
+                               1, N, R, _stream(ig))
+    return h
+
+
+class _GruSeq(torch.autograd.Function):
+    """_LstmSeq for two (or one) independent GRUCells: T time-major steps with the per-step episode mask as ONE autograd node;
+    per step one batched hidden GEMM + one cell launch forward, the backward is _gru_bptt.
+    ig0/ig1 [T*N,3R] (input projections incl. b_ih), whh [P,R,3R] (= W_hh^T per player), bhh [P,3R], h0 [P,N,R] (already
+    masked), keep [T,N] float. Returns per player h_seq [T,N,R] (the un-masked step outputs, what the heads read)."""
+
+    @staticmethod
+    def forward(ctx, ig0, ig1, whh, bhh, h0, keep):
+        L = lib()
+        P, N, R = h0.shape
+        T = keep.shape[0]
+        dev = h0.device
+        ig0, whh, bhh, keep = ig0.contiguous(), whh.contiguous(), bhh.contiguous(), keep.contiguous()
+        ig1 = ig1.contiguous() if ig1 is not None else None
+        h_all = torch.empty((P, T + 1, N, R), dtype=torch.float32, device=dev)   # slot 0 = h0, slot t+1 = h_t
+        acts = torch.empty((P, T, N, 4 * R), dtype=torch.float32, device=dev)    # (r, z, n, q)
+        h_all[:, 0].copy_(h0)
+        hg = torch.empty((P, N, 3 * R), dtype=torch.float32, device=dev)
+        st = _stream(h0)
+        ps, pa, step, astep, istep = (T + 1) * N * R, T * N * 4 * R, N * R * 4, N * 4 * R * 4, N * 3 * R * 4
+        for t in range(T):
+            torch.bmm(h_all[:, t], whh, out=hg)
+            L.atr_gru_cell_forward(
+                C.c_void_p(ig0.data_ptr() + t * istep), C.c_void_p(ig1.data_ptr() + t * istep) if ig1 is not None else None,
+                _p(hg), _p(bhh[0]), _p(bhh[1]) if P > 1 else None, C.c_void_p(h_all.data_ptr() + t * step), ps,
+                _p(keep[t - 1]) if t else None, None, C.c_void_p(h_all.data_ptr() + (t + 1) * step), ps,
+                C.c_void_p(acts.data_ptr() + t * astep), pa, P, N, R, st)
+        ctx.save_for_backward(whh, keep, h_all, acts)
+        ctx.two = ig1 is not None
+        return tuple(h_all[p, 1:] for p in range(P))                             # per player [T,N,R], contiguous
+
+    @staticmethod
+    def backward(ctx, *dhs):
+        whh, keep, h_all, acts = ctx.saved_tensors
+        R = h_all.shape[-1]
+        dG, dh0, dwhh, dbhh = _gru_bptt(whh, keep, h_all, acts, dhs)
+        return dG[0][:, :3 * R], (dG[1][:, :3 * R] if ctx.two else None), dwhh, dbhh, dh0, None
+
+
+def gru_sequence(ig0, ig1, whh, bhh, h0, keep):
+    return _GruSeq.apply(ig0, ig1, whh, bhh, h0, keep)
+
+
+use_fused_gru_bptt = True   # the GRU recurrence backward as ONE launch (atr_gru_bptt) instead of 2 launches per step
+
+
+def _hidden_cols(x, R):
+    """The hidden-side columns (r, z, q) of a [..., 4R] tensor laid out as dG is: (dr_pre, dz_pre, dn_pre, dn_pre r)."""
+    return torch.cat([x[..., :2 * R], x[..., 3 * R:]], -1)
+
+
+def _gru_bptt(whh, keep, h_all, acts, dhs):
+    """Back-propagation through time over a GRU recurrence's stored activations: whh [P,R,3R], keep [T,N], h_all [P,T+1,N,R],
+    acts [P,T,N,4R] = (r, z, n, q), dhs = per-player dL/dh_seq [T,N,R] (None = zero). Returns dG [P, T*N, 4R] = (dr_pre, dz_pre,
+    dn_pre, dn_pre r) — columns 0:3R are dL/d ig —, dL/dh0 [P,N,R], dL/dW_hh^T [P,R,3R] and dL/db_hh [P,3R]."""
+    L = lib()
+    P, T1, N, R = h_all.shape
+    T = T1 - 1
+    dev = h_all.device
+    dG = torch.empty((P, T, N, 4 * R), dtype=torch.float32, device=dev)
+    dhn = torch.empty((P, N, R), dtype=torch.float32, device=dev)
+    st = _stream(h_all)
+    ps, pa, step, astep = (T + 1) * N * R, T * N * 4 * R, N * R * 4, N * 4 * R * 4
+    whh_nn = whh.transpose(1, 2)                                                  # [P,3R,R]: nn.GRUCell's weight_hh
+    if use_fused_gru_bptt and R == 128 and h_all.is_cuda and all(t.is_contiguous() for t in (h_all, acts, keep)):
+        whh_nn = whh_nn.contiguous()
+        dh_c = [d.contiguous() if d is not None else None for d in dhs]
+        L.atr_gru_bptt(_pn(dh_c[0]), _pn(dh_c[1]) if P > 1 else None, _p(keep), _p(acts), pa, _p(h_all), ps, _p(whh_nn[0]),
+                       _p(whh_nn[1]) if P > 1 else None, _p(dG), pa, _p(dhn), P, T, N, R, st)
+    else:
+        dhs = [torch.zeros((T, N, R), dtype=torch.float32, device=dev) if d is None else d.contiguous() for d in dhs]
+        pd = (dhs[1].data_ptr() - dhs[0].data_ptr()) // 4 if P > 1 else 0          # player stride between the two grads
+        # weight_hh with a zero block under dG's dn_pre columns: the step's hidden GEMM reads dG's rows as they are
+        w4 = torch.cat([whh_nn[:, :2 * R], whh_nn.new_zeros((P, R, R)), whh_nn[:, 2 * R:]], 1)      # [P,4R,R]
+        for t in range(T - 1, -1, -1):
+            L.atr_gru_cell_backward(
+                C.c_void_p(dhs[0].data_ptr() + t * step), pd, _p(dhn), _p(keep[t]), _p(keep[t - 1]) if t else None,
+                C.c_void_p(acts.data_ptr() + t * astep), pa, C.c_void_p(h_all.data_ptr() + t * step), ps,
+                C.c_void_p(dG.data_ptr() + t * astep), pa, 1 if t < T - 1 else 0, P, N, R, st)
+            dhn.baddbmm_(dG[:, t], w4)                                            # + dG_t W_hh: the gradient into k h_{t-1}
+    # W_hh: sum_t (k_{t-1} h_{t-1})^T dG_t[hidden columns] as one GEMM per player over all T*N rows; b_hh: their column sums
+    dG = dG.view(P, T * N, 4 * R)
+    hm = (h_all[:, :T] * _keep_prev(keep).view(1, T, N, 1)).view(P, T * N, R)
+    dwhh = _hidden_cols(torch.bmm(hm.transpose(1, 2), dG), R)
+    dbhh = _hidden_cols(dG.sum(1), R)
+    return dG, dhn, dwhh, dbhh
 
 
 class _LstmSeqCached(torch.autograd.Function):

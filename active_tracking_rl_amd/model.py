@@ -10,8 +10,10 @@ The reference networks are structurally batch-1 (`x.view(1, -1)`, perception.py:
   hx, cx  [N, A, rnn_out]                 (or [A, rnn_out])
 and `view(N, -1)` keeps the per-env feature order of the reference, including the
 [tracker frame, target frame] concatenation the TAT target uses (model.py:255).
-Only the discrete maze heads are built ('maze' encoders, 'lstm' core); the continuous / Unreal image heads
-(CNN_simple, ICML, GRU) are outside the hot-path scope.
+Only the discrete maze heads are built ('maze' encoders, 'lstm' or 'gru' core: maze-lstm, tat-maze-lstm, maze-gru,
+tat-maze-gru); the continuous / Unreal image heads (CNN_simple, ICML) are outside the hot-path scope.
+The GRU cores keep the reference's names too (the module is still called `lstm`) and run on the path without a rollout
+cache: A3C_Dueling.act, forward_sequence -> gru_sequence (include/atr_gru.h).
 """
 import numpy as np
 import torch
@@ -134,6 +136,71 @@ def lstm_sequence(lstms, feats, h, c, keep):
         outs.append(h)
         h, c = h * keepm[t], c * keepm[t]
     return torch.stack(outs, 0).view(T, P, N, R), h.view(P, N, R), c.view(P, N, R)
+
+
+fused_gru = True    # GPU tensors: the GRU recurrence through csrc/gru_hip.hip (fused.gru_cell / gru_sequence); False = ATen ops
+
+
+def gru_sequence_fused(cells, feats, h, c, keep):
+    """gru_sequence on the HIP kernels: feats = per-player list of [T, N, F]. One autograd node for the whole recurrence
+    (fused.gru_sequence); h_seq comes back as a per-player list of [T, N, R]."""
+    from . import fused
+    T, N = feats[0].shape[0], feats[0].shape[1]
+    igs = [F.linear(f.reshape(T * N, -1), l.weight_ih, l.bias_ih) for f, l in zip(feats, cells)]
+    whh = torch.stack([l.weight_hh.t() for l in cells], 0)
+    bhh = torch.stack([l.bias_hh for l in cells], 0)
+    h_seq = list(fused.gru_sequence(igs[0], igs[1] if len(igs) > 1 else None, whh, bhh, h.contiguous(), keep))
+    return h_seq, torch.stack([o[-1] for o in h_seq], 0) * keep[-1].view(1, N, 1), c * keep.prod(0).view(1, N, 1)
+
+
+def gru_sequence(cells, feats, h, c, keep):
+    """lstm_sequence's twin for P independent nn.GRUCells (gate order r, z, n): same arguments, same triple back. Step t reads
+    k_{t-1} h_{t-1}; b_hh cannot be folded into the input projection (b_hn sits inside r * (.)), so only b_ih is. The cell
+    state is not part of a GRU: c [P, N, R] rides along and comes back masked by every step's keep (what Agent does to cxs).
+    feats [T, P, N, F] or a per-player list of [T, N, F]; the list form on the GPU selects the HIP recurrence
+    (gru_sequence_fused), anything else — CPU tensors, float64, fused_gru off — these ATen ops."""
+    if isinstance(feats, (list, tuple)):
+        f0 = feats[0]
+        if f0.is_cuda and fused_gru and len(feats) <= 2 and h.shape[-1] % 4 == 0 and f0.dtype == torch.float32:
+            return gru_sequence_fused(cells, list(feats), h, c, keep)
+        feats = torch.stack(list(feats), 1)
+    T, P, N = feats.shape[0], feats.shape[1], feats.shape[2]
+    R = h.shape[-1]
+    ig = torch.stack([F.linear(feats[:, p].reshape(T * N, -1), l.weight_ih, l.bias_ih).view(T, N, -1)
+                      for p, l in enumerate(cells)], 1)                       # [T, P, N, 3R]
+    igates = ig.unbind(0)
+    whh = torch.stack([l.weight_hh.t() for l in cells], 0)                     # [P, R, 3R]
+    bhh = torch.stack([l.bias_hh for l in cells], 0).unsqueeze(1)              # [P, 1, 3R]
+    keepm = keep.view(T, 1, N, 1).unbind(0)
+    outs = []
+    for t in range(T):
+        i_r, i_z, i_n = igates[t].chunk(3, -1)
+        h_r, h_z, h_n = (torch.bmm(h, whh) + bhh).chunk(3, -1)
+        r, z = torch.sigmoid(i_r + h_r), torch.sigmoid(i_z + h_z)
+        n = torch.tanh(i_n + r * h_n)
+        h = (1 - z) * n + z * h
+        outs.append(h)
+        h = h * keepm[t]
+    return torch.stack(outs, 0), h, c * keep.prod(0).view(1, N, 1)
+
+
+def _recurrence(cell):
+    """The sequence function of a recurrent core: lstm_sequence or gru_sequence."""
+    return gru_sequence if isinstance(cell, nn.GRUCell) else lstm_sequence
+
+
+def _make_core(head_name, feature_dim, rnn_out):
+    """The recurrent core the network name selects (model.py:115-124 of the reference), its biases zero-filled. Whatever the
+    core, the module is called `lstm` (the reference's state-dict names)."""
+    if 'lstm' in head_name:
+        core = nn.LSTMCell(feature_dim, rnn_out)
+    elif 'gru' in head_name:
+        core = nn.GRUCell(feature_dim, rnn_out)
+    else:
+        raise NotImplementedError("only LSTM and GRU cores are in scope; got %r" % head_name)
+    core.bias_ih.data.fill_(0)
+    core.bias_hh.data.fill_(0)
+    return core
 
 
 def _player(h_seq, p):
@@ -320,7 +387,8 @@ class CNN_maze(nn.Module):
 
 def _make_encoder(head_name, obs_space, stack_frames):
     if 'maze' not in head_name:
-        raise NotImplementedError("only the 'maze' encoders (maze-lstm, tat-maze-lstm) are in scope; got %r" % head_name)
+        raise NotImplementedError("only the 'maze' encoders (maze-lstm, tat-maze-lstm, maze-gru, tat-maze-gru) are in scope; "
+                                  "got %r" % head_name)
     return CNN_maze(obs_space, stack_frames)
 
 
@@ -334,11 +402,8 @@ class A3C(nn.Module):
         self.head_name = head_name
         self.encoder = _make_encoder(head_name, obs_space, stack_frames)
         feature_dim = self.encoder.outdim
-        if 'lstm' not in head_name:
-            raise NotImplementedError("only LSTM cores are in scope")
-        self.lstm = nn.LSTMCell(feature_dim, rnn_out)
-        self.lstm.bias_ih.data.fill_(0)
-        self.lstm.bias_hh.data.fill_(0)
+        self.lstm = _make_core(head_name, feature_dim, rnn_out)
+        self.gru = isinstance(self.lstm, nn.GRUCell)
         feature_dim = rnn_out
         self.actor = PolicyNet(feature_dim, action_space, head_name, device)
         self.critic = ValueNet(feature_dim)
@@ -348,7 +413,10 @@ class A3C(nn.Module):
     def forward(self, inputs, test=False):
         x, (hx, cx) = inputs
         feature = self.encoder(x)
-        hx, cx = self.lstm(feature, (hx, cx))
+        if self.gru:             # model.py:139-141: cx is left untouched
+            hx = self.lstm(feature, hx)
+        else:
+            hx, cx = self.lstm(feature, (hx, cx))
         value = self.critic(hx)
         action, entropy, log_prob = self.actor(hx, test)
         return value, action, entropy, log_prob, (hx, cx)
@@ -370,7 +438,7 @@ class A3C(nn.Module):
     def forward_sequence(self, x_seq, actions, h, c, keep):
         """Time-batched re-evaluation of T stored steps for this player alone (same math as T calls of forward())."""
         feats = self.sequence_features(x_seq)
-        h_seq, h, c = lstm_sequence([self.lstm], [feats], h.unsqueeze(0), c.unsqueeze(0), keep)
+        h_seq, h, c = _recurrence(self.lstm)([self.lstm], [feats], h.unsqueeze(0), c.unsqueeze(0), keep)
         return self.sequence_heads(_player(h_seq, 0), actions) + ((h[0], c[0]),)
 
 
@@ -384,11 +452,8 @@ class TAT(nn.Module):
         self.head_name = head_name
         self.encoder = _make_encoder(head_name, obs_space, stack_frames)
         feature_dim = self.encoder.outdim
-        if 'lstm' not in head_name:
-            raise NotImplementedError("only LSTM cores are in scope")
-        self.lstm = nn.LSTMCell(feature_dim, rnn_out)
-        self.lstm.bias_ih.data.fill_(0)
-        self.lstm.bias_hh.data.fill_(0)
+        self.lstm = _make_core(head_name, feature_dim, rnn_out)
+        self.gru = isinstance(self.lstm, nn.GRUCell)
         feature_dim = rnn_out
         self.actor = PolicyNet(feature_dim, action_space, head_name, device)
         self.critic = ValueNet(feature_dim)
@@ -404,7 +469,10 @@ class TAT(nn.Module):
     def forward(self, inputs, test=False):
         x, (hx, cx), action_tracker = inputs
         feature = self.encoder(x) + self.fc_action_tracker(action_tracker)
-        hx, cx = self.lstm(feature, (hx, cx))
+        if self.gru:             # model.py:198-200: cx is left untouched
+            hx = self.lstm(feature, hx)
+        else:
+            hx, cx = self.lstm(feature, (hx, cx))
         value = self.critic(hx)
         action, entropy, log_prob = self.actor(hx, test)
         R_pred = self.reward_aux(hx) if self.sub_task else None
@@ -427,7 +495,7 @@ class TAT(nn.Module):
 
     def forward_sequence(self, x_seq, actions, action_tracker, h, c, keep):
         feats = self.sequence_features(x_seq, action_tracker)
-        h_seq, h, c = lstm_sequence([self.lstm], [feats], h.unsqueeze(0), c.unsqueeze(0), keep)
+        h_seq, h, c = _recurrence(self.lstm)([self.lstm], [feats], h.unsqueeze(0), c.unsqueeze(0), keep)
         v, e, l, R_pred = self.sequence_heads(_player(h_seq, 0), actions)
         return v, e, l, (h[0], c[0]), R_pred
 
@@ -490,6 +558,9 @@ class A3C_Dueling(nn.Module):
             else:
                 self.tat = False
                 self.player1 = A3C(obs_shapes[1], action_space[1], rnn_out, head_name, stack_frames, device=device)
+        # whether the rollout cache (new_cache / act_cached / forward_sequence_cached, the graphed evaluator) knows this model's
+        # recurrent core: the LSTM's. A GRU model acts through act() and is re-evaluated by forward_sequence (Agent, evaluator)
+        self.cacheable_core = not self.player0.gru
 
     def cache_dense(self, on=True):
         """Expand the conv weights once per rollout (see CNN_maze.cache_dense)."""
@@ -560,12 +631,30 @@ class A3C_Dueling(nn.Module):
     @torch.no_grad()
     def begin_act(self):
         """Per-rollout constants of act() (the weights do not change inside a rollout): b_ih + b_hh per player."""
+        if not self.cacheable_core:      # (a GRU's b_hh is added after the mask, inside the cell kernel: nothing to sum)
+            self._bsum = None
+            return
         self._bsum = [l.bias_ih + l.bias_hh for l in (self.player0.lstm, self.player1.lstm)]
+
+    def _act_cell_gru(self, gru, feat, h, c, done):
+        """_act_cell for a GRUCell: on the GPU the mask is applied inside the cell kernel (csrc/gru_hip.hip); c rides along,
+        zeroed where the previous step ended an episode."""
+        if done is not None:
+            c = c.masked_fill(done.view(torch.bool).unsqueeze(1), 0.0)
+        if feat.is_cuda and fused_gru and feat.dtype == torch.float32 and h.shape[1] % 4 == 0:
+            from . import fused
+            return fused.gru_cell(torch.addmm(gru.bias_ih, feat, gru.weight_ih.t()), torch.mm(h, gru.weight_hh.t()),
+                                  gru.bias_hh, h, done=done), c
+        if done is not None:
+            h = h * (done == 0).to(h.dtype).unsqueeze(1)
+        return gru(feat, h), c
 
     def _act_cell(self, i, lstm, feat, h, c, done):
         """One LSTMCell step of the actor. (h, c) are the previous step's UN-masked outputs and `done` [N] uint8 that
         step's done flags (None: nothing pending): on the GPU the mask is applied inside the fused cell kernel
         (csrc/lstm_hip.hip); otherwise here, before nn.LSTMCell."""
+        if not self.cacheable_core:
+            return self._act_cell_gru(lstm, feat, h, c, done)
         if feat.is_cuda and fused_lstm and feat.dtype == torch.float32 and h.shape[1] % 4 == 0:
             from . import fused
             bsum = getattr(self, "_bsum", None)
@@ -614,6 +703,8 @@ class A3C_Dueling(nn.Module):
         then knows the step's done flags and writes the next step's masked hidden rows). Only then is the one-GEMM LSTMCell
         store [features | k h_prev] built: with a separate env.step (RPF / Nav-less 'Full' ids, --rescale, --stack-frames > 1,
         NumpyVecEnv) nobody would write those hidden columns."""
+        if not self.cacheable_core:
+            return None
         p0, p1 = self.player0, self.player1
         ok = (states.is_cuda and states.dtype in (torch.float32, torch.uint8) and fused_lstm and not self.single
               and all(isinstance(p.encoder, CNN_maze) and p.encoder.small and p.encoder.use_fused
@@ -1028,8 +1119,8 @@ class A3C_Dueling(nn.Module):
         else:
             f1 = p1.sequence_features(states_seq[:, :, 1])
         # both players' recurrences in lock step: one bmm + one fused cell per time step for the pair
-        h_seq, _, _ = lstm_sequence([p0.lstm, p1.lstm], [f0, f1],
-                                    hx.transpose(0, 1).contiguous(), cx.transpose(0, 1).contiguous(), keep)
+        h_seq, _, _ = _recurrence(p0.lstm)([p0.lstm, p1.lstm], [f0, f1],
+                                           hx.transpose(0, 1).contiguous(), cx.transpose(0, 1).contiguous(), keep)
         v0, e0, l0 = p0.sequence_heads(_player(h_seq, 0), actions_seq[:, :, 0])
         R_pred = 0
         if self.tat:

@@ -158,6 +158,8 @@ class Agent(object):
             sampler = self.model._sampler = fused.ActionSampler(self.state.device)
         obs0 = self.state.reshape(self._buf[0][0].shape) if self._buf is not None else None
         want_cache = num_steps is not None and self.cache_rollout and hasattr(self.model, "new_cache") and self.num_agents == 2
+        # (a model whose recurrent core the cache does not know — the GRU nets — says so: it acts through model.act)
+        want_cache = want_cache and getattr(self.model, "cacheable_core", True)
         # the rollout's first launch (atr_rollout_begin2) moves the LSTM state and the observation into the stores AND makes the
         # per-rollout constants of the actor + the draw counter's bump: one launch instead of ~8
         one_launch = (want_cache and self.fused_bookkeeping and torch.is_tensor(self.hxs) and self.hxs.is_cuda
@@ -199,6 +201,10 @@ class Agent(object):
             return
         if obs0 is not None:
             self._buf[0][0].copy_(obs0)
+        if not getattr(self.model, "cacheable_core", True):
+            # (the learner re-runs the recurrence from h0 / c0; under the pipelined schedule hxs / cxs are the carry, which the
+            # next rollout overwrites while this rollout's learner may still be running: the GRU path keeps its own copy)
+            self.h0, self.c0 = self.hxs.clone(), self.cxs.clone()
         self._hs = [h.contiguous() for h in self.hxs.unbind(1)]
         self._cs = [c.contiguous() for c in self.cxs.unbind(1)]
         if hasattr(self.model, "begin_act"):
