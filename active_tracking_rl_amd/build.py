@@ -3,6 +3,7 @@
 Every source is compiled to an object of its own (in parallel; only the ones older than their source or any header are
 redone) under csrc/_obj/, then linked into libtrack2d_hip.so next to this file."""
 import os
+import re
 import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
@@ -17,10 +18,15 @@ SOURCES = ["track2d_hip.hip", "stem_hip.hip", "policy_hip.hip", "lstm_hip.hip", 
 HEADERS = ["t2d_device.h", os.path.join("..", "..", "include", "track2d.h"),
            os.path.join("..", "..", "include", "atr_policy.h"), "atr_sample.h", "atr_cell.h",
            os.path.join("..", "..", "include", "track2d_np.h"), os.path.join("..", "..", "include", "atr_eval.h"),
-           os.path.join("..", "..", "include", "atr_stats.h"), os.path.join("..", "..", "include", "atr_gru.h")]
+           os.path.join("..", "..", "include", "atr_stats.h"), os.path.join("..", "..", "include", "atr_gru.h"),
+           os.path.join("..", "..", "include", "atr_gru_step.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wno-unused-result"]
 LDFLAGS = ["--offload-arch=gfx950", "-fPIC", "-shared", "-ldl"]
+# kernels that must not spill (source -> a part of their mangled names): the compiler's resource remarks are read when the source is
+# compiled, and scratch > 0 bytes per lane in one of them fails the build (k_gru_step: the LSTM forms of the step have none)
+NO_SCRATCH = {"track2d_hip.hip": "k_gru_step"}
+REMARKS = "-Rpass-analysis=kernel-resource-usage"
 
 
 def _newest_header():
@@ -43,6 +49,24 @@ def needs_build():
     return any(os.path.getmtime(os.path.join(CSRC, f)) > t for f in SOURCES + HEADERS)
 
 
+def scratch_users(remarks, part):
+    """The (mangled name, bytes per lane) of every kernel whose name holds `part` and that uses scratch memory, read from the
+    compiler's kernel-resource-usage remarks; an error if the remarks name no such kernel (the check would check nothing)."""
+    name, seen, bad = None, 0, []
+    for line in remarks.splitlines():
+        m = re.search(r"remark:\s+Function Name: (\S+)", line)
+        if m:
+            name = m.group(1)
+            seen += part in name
+            continue
+        m = re.search(r"remark:\s+ScratchSize \[bytes/lane\]: (\d+)", line)
+        if m and name is not None and part in name and int(m.group(1)) != 0:
+            bad.append((name, int(m.group(1))))
+    if not seen:
+        raise RuntimeError("no resource remark names a %s kernel: the scratch check found nothing to check" % part)
+    return bad
+
+
 def build(force=False, verbose=False):
     """Compile csrc/*.hip into libtrack2d_hip.so next to this file (hipcc cross-compiles without a GPU)."""
     if not force and not needs_build():
@@ -55,7 +79,18 @@ def build(force=False, verbose=False):
         cmd = [HIPCC] + CFLAGS + ["-c", os.path.join(CSRC, src), "-o", _obj(src)]
         if verbose:
             print(" ".join(cmd), flush=True)
-        subprocess.check_call(cmd)
+        if src not in NO_SCRATCH:
+            subprocess.check_call(cmd)
+            return
+        r = subprocess.run(cmd + [REMARKS], stderr=subprocess.PIPE, text=True)
+        if r.returncode != 0:
+            sys.stderr.write(r.stderr)
+            raise subprocess.CalledProcessError(r.returncode, cmd)
+        sys.stderr.write("".join(l + "\n" for l in r.stderr.splitlines() if "warning:" in l))
+        bad = scratch_users(r.stderr, NO_SCRATCH[src])
+        if bad:
+            os.remove(_obj(src))
+            raise RuntimeError("%s: scratch memory in %s" % (src, ", ".join("%s (%d bytes per lane)" % b for b in bad)))
     with ThreadPoolExecutor(max_workers=min(len(todo), os.cpu_count() or 4) or 1) as pool:
         list(pool.map(compile_one, todo))
     cmd = [HIPCC] + LDFLAGS + ["-o", LIB] + [_obj(s) for s in SOURCES]

@@ -38,6 +38,24 @@ __device__ __forceinline__ CellOut cell4(const float4 &pi, const float4 &pf, con
     return r;
 }
 
+// torch.nn.GRUCell for four hidden units (gate order r, z, n; include/atr_gru.h), from the step's ONE 4R-wide gate product over
+// [features | k h_prev] rows with its biases already added: pr = r's pre-activation, pz = z's, pn = ig_n + b_in, pq = k hg_n + b_hn;
+// hp = k h_prev (masked). r, z, n, q are the backward store of atr_gru_cell_backward / atr_gru_bptt; h' = (1 - z) n + z (k h_prev)
+// (the expressions of k_gru_cell_fwd, csrc/gru_hip.hip)
+struct GruOut { float4 r, z, n, q, h; };
+__device__ __forceinline__ GruOut gru_cell4(const float4 &pr, const float4 &pz, const float4 &pn, const float4 &pq, const float4 &hp)
+{
+    GruOut o;
+    o.r = make_float4(sigmoidf_(pr.x), sigmoidf_(pr.y), sigmoidf_(pr.z), sigmoidf_(pr.w));
+    o.z = make_float4(sigmoidf_(pz.x), sigmoidf_(pz.y), sigmoidf_(pz.z), sigmoidf_(pz.w));
+    o.q = pq;
+    o.n = make_float4(tanhf_(pn.x + o.r.x * pq.x), tanhf_(pn.y + o.r.y * pq.y), tanhf_(pn.z + o.r.z * pq.z),
+                      tanhf_(pn.w + o.r.w * pq.w));
+    o.h = make_float4((1.0f - o.z.x) * o.n.x + o.z.x * hp.x, (1.0f - o.z.y) * o.n.y + o.z.y * hp.y,
+                      (1.0f - o.z.z) * o.n.z + o.z.z * hp.z, (1.0f - o.z.w) * o.n.w + o.z.w * hp.w);
+    return o;
+}
+
 // actor head on a fresh hidden row held four units per lane by `rq` consecutive lanes (rq = R / 4, a power of two <= 64
 // that divides the wave): this lane's partial logits over its four units, then the butterfly sum over the row's lanes
 __device__ __forceinline__ void head_logits(const float4 &h, const float4 (&aw)[kMaxActions], int A, int rq,

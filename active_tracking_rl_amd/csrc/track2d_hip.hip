@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../../include/atr_eval.h"
+#include "../../include/atr_gru_step.h"
 #include "../../include/atr_policy.h"
 #include "../../include/track2d.h"
 #include "../../include/track2d_np.h"
@@ -1939,11 +1940,18 @@ __global__ __launch_bounds__(64 * kStep2Waves) void k_step2(DevState s, const vo
 // draw — same logits, same lane, *a.counter is not read — and the env's leader lane keeps the evaluator's episode accounts
 // (ev_rsum f32 [N,2], ev_len i32 [N], ev_alive u8 [N]) with the step's reward and done flag still in its registers: plain
 // per-lane loads and stores of its own env's slots, no cross-lane traffic, no barrier. GREEDY = false is the code as it was.
-template <int OBS, bool RAM, bool ENV, int NA, bool NAV, bool STAGE_EMB, int NTHREADS, bool GREEDY = false>
+// GRU (atr_gru_act_env_step / atr_gru_eval_act_env_step, include/atr_gru_step.h): both cells are nn.GRUCell (gru_cell4 of
+// atr_cell.h). a.ig[p] is the step's ONE 4R-wide product over [features | k h_prev] rows — (r_pre, z_pre, ig_n, k hg_n) —,
+// a.bias[p] its bias (b_ir + b_hr, b_iz + b_hz, b_in, b_hn), a.emb the embedding rows with zeros under the hg_n columns; the masked
+// previous hidden row comes from gr (the h columns of this step's rows: the mask is already in them, so done_prev is not read);
+// no cell state is read or written, a.acts[p] receives (r, z, n, q). Everything after the cell is the LSTM form's code.
+// GRU = false is the code as it was.
+struct GruRows { const float *h[2]; long long ld; };      // per player k h_prev [N, R], row stride ld floats
+template <int OBS, bool RAM, bool ENV, int NA, bool NAV, bool STAGE_EMB, int NTHREADS, bool GREEDY = false, bool GRU = false>
 __device__ __forceinline__ void act_pair(const DevState &s, const atr_act_step &a, void *obs, float *rew, uint8_t *done_out,
                                          uint32_t stamp, int e0, int lane, int tid, uint32_t *stage, uint32_t *navtile,
                                          float *emb_lds, float *ev_rsum = nullptr, int *ev_len = nullptr,
-                                         uint8_t *ev_alive = nullptr)
+                                         uint8_t *ev_alive = nullptr, const GruRows *gr = nullptr)
 {
     using namespace atr;
     static_assert(!GREEDY || ENV, "the evaluation step always steps the env");
@@ -1965,7 +1973,7 @@ __device__ __forceinline__ void act_pair(const DevState &s, const atr_act_step &
     constexpr int R = 128;
     // ... then everything both cells read, in one batch. The gate pre-activations are touched exactly once (written by the
     // GEMM just before, never read again): non-temporal loads keep them from displacing the weights in L2.
-    const float k = a.done_prev ? (a.done_prev[e] == 0 ? 1.0f : 0.0f) : 1.0f;
+    const float k = GRU ? 1.0f : (a.done_prev ? (a.done_prev[e] == 0 ? 1.0f : 0.0f) : 1.0f);
     float4 pre[2][4], cp[2], aw[2][NA];
     auto ldnt = [](const float *p_) {
         const float4 *q_ = reinterpret_cast<const float4 *>(p_);
@@ -1975,7 +1983,7 @@ __device__ __forceinline__ void act_pair(const DevState &s, const atr_act_step &
     // a.ig[0] == NULL (round 6): the tracker's cell already ran — as the epilogue of the step's LSTMCell product (atr_gate_cell,
     // csrc/gate_cell_hip.hip) — and h_out[0] / c_out[0] hold its fresh state: nothing of its gates is read here, its hidden row
     // is (wave-uniform branch: the argument is the same for every lane of the launch)
-    const bool pre0 = a.ig[0] == nullptr;
+    const bool pre0 = !GRU && a.ig[0] == nullptr;
     float4 h0_pre = make_float4(0.f, 0.f, 0.f, 0.f);
     if (pre0) h0_pre = ld4(a.h_out[0] + (size_t)e * R + j);
 #pragma unroll
@@ -1986,6 +1994,12 @@ __device__ __forceinline__ void act_pair(const DevState &s, const atr_act_step &
         const float *ig = a.ig[p] + (size_t)e * 4 * R + j;
 #pragma unroll
         for (int g = 0; g < 4; g++) pre[p][g] = ldnt(ig + g * R);
+        if (GRU) {      // the bias is always there (b_hn has no other way in); cp = the masked previous hidden row
+#pragma unroll
+            for (int g = 0; g < 4; g++) pre[p][g] = fma4(1.0f, ld4(a.bias[p] + g * R + j), pre[p][g]);
+            cp[p] = ld4(gr->h[p] + (size_t)e * gr->ld + j);
+            continue;
+        }
         if (a.hg[p]) {
             const float *hg = a.hg[p] + (size_t)e * 4 * R + j;
 #pragma unroll
@@ -2028,18 +2042,28 @@ __device__ __forceinline__ void act_pair(const DevState &s, const atr_act_step &
             for (int g = 0; g < 4; g++) pre[1][g] = fma4(1.0f, ld4(em + g * R), pre[1][g]);
         }
         CellOut o;
-        if (p == 0 && pre0) o.h = h0_pre;
+        auto stnt = [](float *d_, const float4 &v_) {
+            __builtin_nontemporal_store(v_.x, d_); __builtin_nontemporal_store(v_.y, d_ + 1);
+            __builtin_nontemporal_store(v_.z, d_ + 2); __builtin_nontemporal_store(v_.w, d_ + 3);
+        };
+        if (GRU) {
+            const GruOut u = gru_cell4(pre[p][0], pre[p][1], pre[p][2], pre[p][3], cp[p]);
+            o.h = u.h;
+            if (live) {
+                st4(a.h_out[p] + (size_t)e * R + j, u.h);
+                if (a.acts[p]) {   // (r, z, n, q): what atr_gru_bptt reads, a whole rollout later
+                    float *ac = a.acts[p] + (size_t)e * 4 * R + j;
+                    stnt(ac, u.r); stnt(ac + R, u.z); stnt(ac + 2 * R, u.n); stnt(ac + 3 * R, u.q);
+                }
+            }
+        } else if (p == 0 && pre0) o.h = h0_pre;
         else o = cell4(pre[p][0], pre[p][1], pre[p][2], pre[p][3], cp[p], k);
         hkeep[p] = o.h;
-        if (live && !(p == 0 && pre0)) {
+        if (!GRU && live && !(p == 0 && pre0)) {
             st4(a.h_out[p] + (size_t)e * R + j, o.h);
             st4(a.c_out[p] + (size_t)e * R + j, o.c);
             if (a.acts[p]) {   // read next by the learner, a whole rollout later: streamed past the caches
                 float *ac = a.acts[p] + (size_t)e * 4 * R + j;
-                auto stnt = [](float *d_, const float4 &v_) {
-                    __builtin_nontemporal_store(v_.x, d_); __builtin_nontemporal_store(v_.y, d_ + 1);
-                    __builtin_nontemporal_store(v_.z, d_ + 2); __builtin_nontemporal_store(v_.w, d_ + 3);
-                };
                 stnt(ac, o.gi); stnt(ac + R, o.gf); stnt(ac + 2 * R, o.gg); stnt(ac + 3 * R, o.go);
             }
         }
@@ -2123,6 +2147,23 @@ __global__ __launch_bounds__(64 * kStep2Waves) void k_eval_step(DevState s, atr_
     act_pair<OBS, RAM, true, NA, NAV, true, 64 * kStep2Waves, true>(s, a, obs, rew, done_out, stamp, e0, lane, (int)threadIdx.x,
                                                                     stage2[wave], navtiles[NAV ? wave : 0], emb_lds, ev.rsum,
                                                                     ev.length, ev.alive);
+}
+
+// The GRU cores' form of k_act_step / k_eval_step (atr_gru_act_env_step, atr_gru_eval_act_env_step): the GRU instantiation of
+// act_pair, with the masked previous hidden rows as its extra input. ev is read by the GREEDY form only.
+template <int OBS, bool RAM, bool ENV, int NA, bool NAV, bool GREEDY>
+__global__ __launch_bounds__(64 * kStep2Waves) void k_gru_step(DevState s, atr_act_step a, GruRows gr, atr_eval_out ev, void *obs,
+                                                               float *rew, uint8_t *done_out, uint32_t stamp)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t stage2[kStep2Waves][kStage2Words];
+    __shared__ __attribute__((aligned(16))) float emb_lds[NA * 4 * 128];
+    __shared__ __attribute__((aligned(16))) uint32_t navtiles[NAV ? kStep2Waves : 1][NAV ? kTileWords : 4];
+    const int lane = (int)(threadIdx.x & 63u);
+    const int wave = uni((int)(threadIdx.x >> 6));
+    const int e0 = ((int)blockIdx.x * kStep2Waves + wave) * 2;
+    act_pair<OBS, RAM, ENV, NA, NAV, true, 64 * kStep2Waves, GREEDY, true>(s, a, obs, rew, done_out, stamp, e0, lane, (int)threadIdx.x,
+                                                                           stage2[wave], navtiles[NAV ? wave : 0], emb_lds, ev.rsum,
+                                                                           ev.length, ev.alive, &gr);
 }
 
 // ---- the small-shard rollout step as ONE launch after the stem: fc + ReLU -> LSTMCell GEMM -> cells + heads + draws + env step ----
@@ -2969,13 +3010,20 @@ extern "C" int t2d_step_u8(t2d_handle *h, const void *act_tracker_dev, const voi
 // The rollout step's last launch (see k_act_step): policy cells + draws + env step. Same stamping / generator schedule
 // as t2d_step.
 // ev != NULL: the evaluation form (atr_eval_act_env_step: greedy actions + episode accounting, k_eval_step); fn names the entry
-// point in the error text.
+// point in the error text. gr != NULL: the GRU cores' form (atr_gru_act_env_step / atr_gru_eval_act_env_step, k_gru_step).
 static int act_env_step_impl(t2d_handle *h, const atr_act_step *args, const atr_eval_out *ev, void *obs_dev, int obs_is_u8,
-                             float *rew_dev, uint8_t *done_dev, void *stream, const char *fn)
+                             float *rew_dev, uint8_t *done_dev, void *stream, const char *fn, const GruRows *gr = nullptr)
 {
     if (!args) return fail(T2D_ERR_INVALID, "%s: null argument", fn);
     const atr_act_step &a = *args;
-    for (int p = 0; p < 2; p++)
+    if (gr) {
+        for (int p = 0; p < 2; p++)
+            if (!a.ig[p] || !a.bias[p] || a.hg[p] || !gr->h[p] || !a.h_out[p] || !a.actor_w[p] || !a.actor_b[p])
+                return fail(T2D_ERR_INVALID, "%s: needs ig, bias, h_prev rows, h_out and the actor per player, and no hg (player %d)", fn, p);
+        if (gr->ld < a.R || (gr->ld & 3) || (((uintptr_t)gr->h[0] | (uintptr_t)gr->h[1]) & 15u))
+            return fail(T2D_ERR_INVALID, "%s: h_prev rows must be 16-byte aligned, their stride >= R and a multiple of 4", fn);
+    }
+    for (int p = 0; p < 2 && !gr; p++)
         if ((!a.ig[p] && p != 0) || !a.h_out[p] || !a.actor_w[p] || !a.actor_b[p] || (a.ig[p] && (!a.c_prev[p] || !a.c_out[p])))
             return fail(T2D_ERR_INVALID, "%s: null policy buffer (player %d)", fn, p);
     if (!a.ig[0] && (a.hg[0] || a.acts[0]))
@@ -2992,7 +3040,15 @@ static int act_env_step_impl(t2d_handle *h, const atr_act_step *args, const atr_
         DevState none;
         std::memset(&none, 0, sizeof(none));
         const unsigned grid = (unsigned)(((a.N + 1) / 2 + kStep2Waves - 1) / kStep2Waves);
-        if (a.A == 4)
+        if (gr) {
+            const atr_eval_out no_ev = {nullptr, nullptr, nullptr};
+            if (a.A == 4)
+                hipLaunchKernelGGL((k_gru_step<OBS_U8, false, false, 4, false, false>), dim3(grid), dim3(64 * kStep2Waves), 0, st, none,
+                                   a, *gr, no_ev, nullptr, nullptr, nullptr, 0u);
+            else
+                hipLaunchKernelGGL((k_gru_step<OBS_U8, false, false, 8, false, false>), dim3(grid), dim3(64 * kStep2Waves), 0, st, none,
+                                   a, *gr, no_ev, nullptr, nullptr, nullptr, 0u);
+        } else if (a.A == 4)
             hipLaunchKernelGGL((k_act_step<OBS_U8, false, false, 4>), dim3(grid), dim3(64 * kStep2Waves), 0, st, none, a, nullptr,
                                nullptr, nullptr, 0u);
         else
@@ -3019,9 +3075,16 @@ static int act_env_step_impl(t2d_handle *h, const atr_act_step *args, const atr_
         h->phase++;
     }
     const int kind = obs_is_u8 ? OBS_U8 : ((((uintptr_t)obs_dev & 15u) == 0u) ? OBS_F32_VEC4 : OBS_F32_SCALAR);
+    const atr_eval_out no_ev = {nullptr, nullptr, nullptr};
 #define T2D_LAUNCH_ACT2(KIND, RAMV, NAV, NAVF)                                                                          \
     do {                                                                                                               \
-        if (ev)                                                                                                        \
+        if (gr && ev)                                                                                                  \
+            hipLaunchKernelGGL((k_gru_step<KIND, RAMV, true, NAV, NAVF, true>), pair_grid(h->s.n), dim3(64 * kStep2Waves), 0, st, \
+                               h->s, a, *gr, *ev, obs_dev, rew_dev, done_dev, h->phase);                               \
+        else if (gr)                                                                                                   \
+            hipLaunchKernelGGL((k_gru_step<KIND, RAMV, true, NAV, NAVF, false>), pair_grid(h->s.n), dim3(64 * kStep2Waves), 0, st, \
+                               h->s, a, *gr, no_ev, obs_dev, rew_dev, done_dev, h->phase);                             \
+        else if (ev)                                                                                                   \
             hipLaunchKernelGGL((k_eval_step<KIND, RAMV, NAV, NAVF>), pair_grid(h->s.n), dim3(64 * kStep2Waves), 0, st, h->s, a, \
                                *ev, obs_dev, rew_dev, done_dev, h->phase);                                             \
         else                                                                                                           \
@@ -3061,6 +3124,28 @@ extern "C" int atr_eval_act_env_step(t2d_handle *h, const atr_act_step *args, co
     if (((uintptr_t)out->rsum & 7u) != 0u || ((uintptr_t)out->length & 3u) != 0u)
         return fail(T2D_ERR_INVALID, "atr_eval_act_env_step: rsum must be 8-byte aligned, length 4-byte aligned");
     return act_env_step_impl(h, args, out, obs_dev, obs_is_u8, rew_dev, done_dev, stream, "atr_eval_act_env_step");
+}
+
+// The GRU cores' step (include/atr_gru_step.h): atr_act_env_step / atr_eval_act_env_step with nn.GRUCell in place of nn.LSTMCell.
+extern "C" int atr_gru_act_env_step(t2d_handle *h, const atr_act_step *args, const float *h_prev0, const float *h_prev1,
+                                    long long h_prev_ld, void *obs_dev, int obs_is_u8, float *rew_dev, uint8_t *done_dev,
+                                    void *stream)
+{
+    const GruRows gr = {{h_prev0, h_prev1}, h_prev_ld};
+    return act_env_step_impl(h, args, nullptr, obs_dev, obs_is_u8, rew_dev, done_dev, stream, "atr_gru_act_env_step", &gr);
+}
+
+extern "C" int atr_gru_eval_act_env_step(t2d_handle *h, const atr_act_step *args, const float *h_prev0, const float *h_prev1,
+                                         long long h_prev_ld, const atr_eval_out *out, void *obs_dev, int obs_is_u8,
+                                         float *rew_dev, uint8_t *done_dev, void *stream)
+{
+    if (!h) return fail(T2D_ERR_INVALID, "atr_gru_eval_act_env_step: needs an env handle (the evaluation step always steps the env)");
+    if (!out || !out->rsum || !out->length || !out->alive)
+        return fail(T2D_ERR_INVALID, "atr_gru_eval_act_env_step: null accounting buffer (rsum, length, alive)");
+    if (((uintptr_t)out->rsum & 7u) != 0u || ((uintptr_t)out->length & 3u) != 0u)
+        return fail(T2D_ERR_INVALID, "atr_gru_eval_act_env_step: rsum must be 8-byte aligned, length 4-byte aligned");
+    const GruRows gr = {{h_prev0, h_prev1}, h_prev_ld};
+    return act_env_step_impl(h, args, out, obs_dev, obs_is_u8, rew_dev, done_dev, stream, "atr_gru_eval_act_env_step", &gr);
 }
 
 // The small-shard rollout step after the stem as ONE launch (k_coop_step): fc + ReLU of both encoders, the LSTMCell GEMM of

@@ -63,16 +63,28 @@ def lib():
     return _lib
 
 
-def eval_act_env_step(env_core, act_args, eval_out, env_out, stream):
-    """atr_eval_act_env_step on fused.act_env_step's arguments (act_args: its fused.ActStepArgs); eval_out = (rsum f32 [N,2],
-    length i32 [N], alive u8 [N]), contiguous, on the env's device."""
+def _eval_out(act_args, eval_out):
+    """EvalOut of eval_out = (rsum f32 [N,2], length i32 [N], alive u8 [N]), contiguous, on the env's device."""
     rsum, length, alive = eval_out
     n = act_args.N
     assert rsum.dtype == torch.float32 and rsum.shape == (n, 2) and rsum.is_contiguous()
     assert length.dtype == torch.int32 and length.shape == (n,) and length.is_contiguous()
     assert alive.dtype == torch.uint8 and alive.shape == (n,) and alive.is_contiguous()
-    out = EvalOut(rsum.data_ptr(), length.data_ptr(), alive.data_ptr())
+    return EvalOut(rsum.data_ptr(), length.data_ptr(), alive.data_ptr())
+
+
+def eval_act_env_step(env_core, act_args, eval_out, env_out, stream):
+    """atr_eval_act_env_step on fused.act_env_step's arguments (act_args: its fused.ActStepArgs); eval_out = (rsum f32 [N,2],
+    length i32 [N], alive u8 [N]), contiguous, on the env's device."""
+    out = _eval_out(act_args, eval_out)
     lib().atr_eval_act_env_step(env_core.h, C.byref(act_args), C.byref(out), *fused._env_out_args(env_out), stream)
+
+
+def gru_eval_act_env_step(env_core, act_args, rows, eval_out, env_out, stream):
+    """atr_gru_eval_act_env_step (include/atr_gru_step.h; bound by fused.lib(): fused.GRU_STEP_PROTOTYPES) on
+    fused.gru_act_env_step's arguments; rows = (k h_prev of player 0, of player 1, their row stride)."""
+    out = _eval_out(act_args, eval_out)
+    fused.lib().atr_gru_eval_act_env_step(env_core.h, C.byref(act_args), *rows, C.byref(out), *fused._env_out_args(env_out), stream)
 
 
 def account(rew, done, rsum=None, length=None, alive=None):
@@ -112,6 +124,8 @@ def supported(env, model):
         return False
     st = torch.empty((env.num_envs, 2, 1, 1) + tuple(buf[0].shape[-2:]), dtype=buf[0].dtype, device=buf[0].device)
     cache = model.new_cache(1, st, env_fused=True)
+    if cache is not None and getattr(cache, "gru", False):       # (--fused-gru: a GRU cache exists in the fused one-GEMM form only)
+        return True
     return cache is not None and cache.f_all is not None and bool(getattr(cache, "has_wih_t", False)) and cache.actions is not None
 
 

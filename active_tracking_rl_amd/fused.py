@@ -183,15 +183,25 @@ GRU_PROTOTYPES = {
     "atr_gru_bptt": (C.c_int, [C.c_void_p] * 4 + [C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p,
                                C.c_longlong, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
 }
+# the GRU cores' fused rollout step, include/atr_gru_step.h (opt-in: --fused-gru; held to the header by tests/test_gru_fused_cpu.py)
+GRU_STEP_PROTOTYPES = {
+    "atr_gru_act_env_step": (C.c_int, [C.c_void_p, C.POINTER(ActStepArgs), C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p,
+                                       C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # (out: evaluator.EvalOut by reference — evaluator.py imports this module, so the class is not named here)
+    "atr_gru_eval_act_env_step": (C.c_int, [C.c_void_p, C.POINTER(ActStepArgs), C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p,
+                                            C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
 # the library's own text for a failed launch, where it keeps one
 _ERROR_DETAIL = {"atr_act_env_step": "t2d_last_error", "atr_coop_env_step": "t2d_last_error", "atr_linear": "atr_lt_last_error"}
+_GRU_STEP_ERROR_DETAIL = {name: "t2d_last_error" for name in GRU_STEP_PROTOTYPES}
 
 
 def _errcheck(name):
     """The ctypes errcheck of a status-returning entry point: a non-zero status raises, 0 is handed back to the caller."""
     def check(status, func=None, args=None):
         if status != 0:
-            detail = ": " + getattr(lib(), _ERROR_DETAIL[name])().decode() if name in _ERROR_DETAIL else ""
+            text = _ERROR_DETAIL.get(name) or _GRU_STEP_ERROR_DETAIL.get(name)
+            detail = ": " + getattr(lib(), text)().decode() if text else ""
             raise RuntimeError("%s failed (%d)%s" % (name, status, detail))
         return status
     return check
@@ -201,7 +211,8 @@ def lib():
     global _lib
     if _lib is None:
         L = vec_env.load_library()
-        for name, (restype, argtypes, *value) in list(ATR_PROTOTYPES.items()) + list(GRU_PROTOTYPES.items()):
+        for name, (restype, argtypes, *value) in (list(ATR_PROTOTYPES.items()) + list(GRU_PROTOTYPES.items())
+                                                  + list(GRU_STEP_PROTOTYPES.items())):
             f = getattr(L, name)
             f.restype, f.argtypes = restype, argtypes
             if restype is C.c_int and not value:
@@ -861,10 +872,12 @@ def _hidden_cols(x, R):
     return torch.cat([x[..., :2 * R], x[..., 3 * R:]], -1)
 
 
-def _gru_bptt(whh, keep, h_all, acts, dhs):
+def _gru_bptt(whh, keep, h_all, acts, dhs, hm=None):
     """Back-propagation through time over a GRU recurrence's stored activations: whh [P,R,3R], keep [T,N], h_all [P,T+1,N,R],
     acts [P,T,N,4R] = (r, z, n, q), dhs = per-player dL/dh_seq [T,N,R] (None = zero). Returns dG [P, T*N, 4R] = (dr_pre, dz_pre,
-    dn_pre, dn_pre r) — columns 0:3R are dL/d ig —, dL/dh0 [P,N,R], dL/dW_hh^T [P,R,3R] and dL/db_hh [P,3R]."""
+    dn_pre, dn_pre r) — columns 0:3R are dL/d ig —, dL/dh0 [P,N,R], dL/dW_hh^T [P,R,3R] and dL/db_hh [P,3R].
+    hm: per player the masked rows k_{t-1} h_{t-1} [T*N,R] where the rollout stored them (row-strided views are fine): dW_hh
+    contracts them as they are."""
     L = lib()
     P, T1, N, R = h_all.shape
     T = T1 - 1
@@ -892,10 +905,60 @@ def _gru_bptt(whh, keep, h_all, acts, dhs):
             dhn.baddbmm_(dG[:, t], w4)                                            # + dG_t W_hh: the gradient into k h_{t-1}
     # W_hh: sum_t (k_{t-1} h_{t-1})^T dG_t[hidden columns] as one GEMM per player over all T*N rows; b_hh: their column sums
     dG = dG.view(P, T * N, 4 * R)
-    hm = (h_all[:, :T] * _keep_prev(keep).view(1, T, N, 1)).view(P, T * N, R)
-    dwhh = _hidden_cols(torch.bmm(hm.transpose(1, 2), dG), R)
+    if hm is not None:
+        dwhh = _hidden_cols(torch.stack([gemm_tn(hm[p], dG[p]) for p in range(P)], 0), R)
+    else:
+        hm = (h_all[:, :T] * _keep_prev(keep).view(1, T, N, 1)).view(P, T * N, R)
+        dwhh = _hidden_cols(torch.bmm(hm.transpose(1, 2), dG), R)
     dbhh = _hidden_cols(dG.sum(1), R)
     return dG, dhn, dwhh, dbhh
+
+
+class _GruSeqCached(torch.autograd.Function):
+    """_LstmSeqCached for the GRU cores (--fused-gru): the input projection + masked recurrence of both players as an autograd node
+    whose forward the rollout already evaluated step by step (gru_act_env_step, same weights): h_all [P,T+1,N,R] and acts
+    [P,T,N,4R] = (r, z, n, q) hold every step. Inputs: per-player features [T*N,F] and GRUCell parameters; output: per-player
+    h_seq [T,N,R]. Backward: _gru_bptt on the stores, then per trained player dfeat = dG[:, :3R] W_ih, dW_ih / d b_ih from one
+    gemm_tn over dG's rows (its fourth column block belongs to the hidden side: d b_hh = the hidden columns' sums), dW_hh from
+    the stored masked rows where the rollout wrote them all. No grouped launch, no embedding fold."""
+
+    @staticmethod
+    def forward(ctx, keep, h_all, acts, opts, *fw):
+        P = h_all.shape[0]
+        need, hm = opts
+        ctx.save_for_backward(keep.contiguous(), h_all, acts, *fw[:3 * P], *(hm if hm is not None else ()))
+        ctx.P, ctx.has_hm = P, hm is not None
+        ctx.need = tuple(bool(x) for x in need) if need is not None else (True,) * P
+        return tuple(h_all[p, 1:] for p in range(P))
+
+    @staticmethod
+    def backward(ctx, *dhs):
+        P = ctx.P
+        keep, h_all, acts = ctx.saved_tensors[:3]
+        feats, wih, whh_nn = (ctx.saved_tensors[3 + i * P:3 + (i + 1) * P] for i in range(3))
+        hm = ctx.saved_tensors[3 + 3 * P:] if ctx.has_hm else None
+        R = h_all.shape[-1]
+        dfeat, dwih, dwhh, dbih, dbhh = ([None] * P for _ in range(5))
+        # (a player the loss does not train — train-mode 0 / 1 — has none of its recurrence back-propagated)
+        groups = [list(range(P))] if all(ctx.need) else [[p] for p in range(P) if ctx.need[p]]
+        for grp in groups:
+            a, b = grp[0], grp[-1] + 1
+            whh = torch.stack([w.t() for w in whh_nn[a:b]], 0)
+            dG, _, dwhh_t, dbhh_g = _gru_bptt(whh, keep, h_all[a:b], acts[a:b], dhs[a:b], hm=hm[a:b] if hm is not None else None)
+            for i, p in enumerate(grp):
+                dfeat[p] = dG[i][:, :3 * R] @ wih[p]
+                dw, cs = gemm_tn(dG[i], feats[p], colsum=True)
+                dwih[p], dbih[p] = dw[:3 * R], cs[:3 * R]
+                dwhh[p], dbhh[p] = dwhh_t[i].t(), dbhh_g[i]
+        return (None, None, None, None) + tuple(dfeat) + tuple(dwih) + tuple(dwhh) + tuple(dbih) + tuple(dbhh)
+
+
+def gru_sequence_cached(cells, feats, keep, h_all, acts, need=None, hm=None):
+    """lstm_sequence_cached for nn.GRUCells: feats per-player [T*N,F] (with grad), the rollout's stores h_all / acts = (r, z, n,
+    q); need per player as there; hm per player the masked previous hidden rows [T*N,R] when the rollout stored every one."""
+    args = list(feats) + [l.weight_ih for l in cells] + [l.weight_hh for l in cells] + [l.bias_ih for l in cells] + \
+        [l.bias_hh for l in cells]
+    return _GruSeqCached.apply(keep, h_all, acts, (need, hm), *args)
 
 
 class _LstmSeqCached(torch.autograd.Function):
@@ -1171,6 +1234,34 @@ def act_env_step(env_core, ig, hg, biases, c_prev, done, h_out, c_out, acts, sam
         lib().atr_act_env_step(None, C.byref(a), None, 0, None, None, _stream(h_out[0]))
     else:
         lib().atr_act_env_step(env_core.h, C.byref(a), *_env_out_args(env_out), _stream(h_out[0]))
+    return actions_out
+
+
+@torch.no_grad()
+def gru_act_env_step(env_core, g, b4, hm_in, h_out, acts, sampler, actors, actions_out, emb=None, env_out=None, hm_out=None,
+                     greedy=False, eval_out=None):
+    """act_env_step for the GRU cores (atr_gru_act_env_step, csrc/track2d_hip.hip k_gru_step; opt-in, --fused-gru): g per-player
+    [N,4R] contiguous = the step's ONE product [features | k h_prev] W4^T (model.gru_step_consts), b4 per-player [4R], hm_in
+    per-player [N,R] views with a common row stride = the masked previous hidden rows (the h columns of this step's rows), h_out
+    per-player [N,R], acts per-player [N,4R] or None: receives (r, z, n, q); emb = E4 [A,4R] or None. No cell state, no done
+    flags (the mask is in the rows). Everything else — draws, ordinals, env_out, hm_out, greedy + eval_out — as act_env_step."""
+    assert hm_out is None or env_core is not None
+    N, R = h_out[0].shape
+    a = _act_step_args(g, None, b4, (None, None), None, h_out, (None, None), acts, sampler, actors, actions_out, emb, hm_out)
+    for p in range(2):
+        assert hm_in[p].shape == (N, R) and hm_in[p].stride(1) == 1 and hm_in[p].dtype == torch.float32
+    assert hm_in[0].stride(0) == hm_in[1].stride(0)
+    rows = (_p(hm_in[0]), _p(hm_in[1]), hm_in[0].stride(0))
+    if greedy:
+        from . import evaluator
+        if env_core is None or eval_out is None:
+            raise RuntimeError("the greedy step exists with the env step and the evaluator's accounts only "
+                               "(atr_gru_eval_act_env_step)")
+        evaluator.gru_eval_act_env_step(env_core, a, rows, eval_out, env_out, _stream(h_out[0]))
+    elif env_core is None:
+        lib().atr_gru_act_env_step(None, C.byref(a), *rows, None, 0, None, None, _stream(h_out[0]))
+    else:
+        lib().atr_gru_act_env_step(env_core.h, C.byref(a), *rows, *_env_out_args(env_out), _stream(h_out[0]))
     return actions_out
 
 

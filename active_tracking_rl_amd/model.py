@@ -13,7 +13,8 @@ and `view(N, -1)` keeps the per-env feature order of the reference, including th
 Only the discrete maze heads are built ('maze' encoders, 'lstm' or 'gru' core: maze-lstm, tat-maze-lstm, maze-gru,
 tat-maze-gru); the continuous / Unreal image heads (CNN_simple, ICML) are outside the hot-path scope.
 The GRU cores keep the reference's names too (the module is still called `lstm`) and run on the path without a rollout
-cache: A3C_Dueling.act, forward_sequence -> gru_sequence (include/atr_gru.h).
+cache: A3C_Dueling.act, forward_sequence -> gru_sequence (include/atr_gru.h) — unless the opt-in fused step is on
+(--fused-gru: gru_step_consts, _new_cache_gru, the GRU branch of _act_step; include/atr_gru_step.h).
 """
 import numpy as np
 import torch
@@ -182,6 +183,32 @@ def gru_sequence(cells, feats, h, c, keep):
         outs.append(h)
         h = h * keepm[t]
     return torch.stack(outs, 0), h, c * keep.prod(0).view(1, N, 1)
+
+
+def gru_step_consts(cells, fa=None):
+    """The constants of the GRU cores' one-product step (include/atr_gru_step.h; --fused-gru), made with tensor ops once per
+    rollout: nn.GRUCell adds its two products only inside the non-linearity (n = tanh(ig_n + r * (hg_n + b_hn))), yet both are ONE
+    4R-wide product over the rows [features | k h_prev] against a block weight per player,
+        W4 [P, 4R, F + R] = [W_ir | W_hr], [W_iz | W_hz], [W_in | 0], [0 | W_hn]     b4 [P, 4R] = (b_ir + b_hr, b_iz + b_hz, b_in, b_hn)
+    whose fourth column block is q = k hg_n + b_hn, where the cell wants b_hn: after the mask. fa = the tracker-aware target's
+    fc_action_tracker: E4 [A, 4R] = ((fa.weight^T + fa.bias) W_ih^T | 0) for the LAST cell (row a = what one_hot(a) adds to its
+    input projection); else None. Returns (W4, b4, E4) in the cells' dtype, on their device."""
+    R, Fd = cells[0].hidden_size, cells[0].weight_ih.shape[1]
+    w = cells[0].weight_ih
+    W4 = w.new_zeros((len(cells), 4 * R, Fd + R))
+    b4 = w.new_empty((len(cells), 4 * R))
+    for p, l in enumerate(cells):
+        W4[p, :3 * R, :Fd] = l.weight_ih
+        W4[p, :2 * R, Fd:] = l.weight_hh[:2 * R]
+        W4[p, 3 * R:, Fd:] = l.weight_hh[2 * R:]
+        b4[p, :2 * R] = l.bias_ih[:2 * R] + l.bias_hh[:2 * R]
+        b4[p, 2 * R:3 * R] = l.bias_ih[2 * R:]
+        b4[p, 3 * R:] = l.bias_hh[2 * R:]
+    E4 = None
+    if fa is not None:
+        E4 = w.new_zeros((fa.weight.shape[1], 4 * R))
+        E4[:, :3 * R] = (fa.weight.t() + fa.bias) @ cells[-1].weight_ih.t()
+    return W4, b4, E4
 
 
 def _recurrence(cell):
@@ -558,9 +585,27 @@ class A3C_Dueling(nn.Module):
             else:
                 self.tat = False
                 self.player1 = A3C(obs_shapes[1], action_space[1], rnn_out, head_name, stack_frames, device=device)
-        # whether the rollout cache (new_cache / act_cached / forward_sequence_cached, the graphed evaluator) knows this model's
-        # recurrent core: the LSTM's. A GRU model acts through act() and is re-evaluated by forward_sequence (Agent, evaluator)
-        self.cacheable_core = not self.player0.gru
+        self.gru_core = self.player0.gru
+        # opt-in (main.py / gym_eval.py --fused-gru, ATR_FUSED_GRU=1; read once, here): a GRU model's rollout as the cached,
+        # env-fused one-GEMM step (k_gru_step) where new_cache's conditions hold; off = the path without a rollout cache
+        # (only the value 1 turns it on: an empty ATR_FUSED_GRU, 0 or a word leave it off)
+        self.fused_gru_step = bool(getattr(args, "fused_gru", False)) or __import__('os').environ.get('ATR_FUSED_GRU') == '1'
+
+    @property
+    def cacheable_core(self):
+        """Whether the rollout cache (new_cache / act_cached / forward_sequence_cached, the graphed evaluator) knows this model's
+        recurrent core: the LSTM's always; a GRU's only with fused_gru_step, on the GPU, in the shapes its one fused form exists
+        for. Otherwise a GRU model acts through act() and is re-evaluated by forward_sequence (Agent, evaluator)."""
+        return True if not self.gru_core else bool(self.fused_gru_step and self._gru_fused_static())
+
+    def _gru_fused_static(self):
+        """What the GRU cores' fused step needs of the model itself (new_cache adds the batch's and the env's side)."""
+        if self.single:
+            return False
+        p0, p1 = self.player0, self.player1
+        R, Fd = p0.lstm.hidden_size, p0.encoder.outdim
+        return bool(p0.lstm.weight_ih.is_cuda and fused_gru and R == 128 and p1.lstm.hidden_size == R and p1.encoder.outdim == Fd
+                    and Fd % 4 == 0 and self._env_fused_static(0, R))
 
     def cache_dense(self, on=True):
         """Expand the conv weights once per rollout (see CNN_maze.cache_dense)."""
@@ -631,7 +676,7 @@ class A3C_Dueling(nn.Module):
     @torch.no_grad()
     def begin_act(self):
         """Per-rollout constants of act() (the weights do not change inside a rollout): b_ih + b_hh per player."""
-        if not self.cacheable_core:      # (a GRU's b_hh is added after the mask, inside the cell kernel: nothing to sum)
+        if self.gru_core:                # (a GRU's b_hh is added after the mask, inside the cell kernel: nothing to sum)
             self._bsum = None
             return
         self._bsum = [l.bias_ih + l.bias_hh for l in (self.player0.lstm, self.player1.lstm)]
@@ -653,7 +698,7 @@ class A3C_Dueling(nn.Module):
         """One LSTMCell step of the actor. (h, c) are the previous step's UN-masked outputs and `done` [N] uint8 that
         step's done flags (None: nothing pending): on the GPU the mask is applied inside the fused cell kernel
         (csrc/lstm_hip.hip); otherwise here, before nn.LSTMCell."""
-        if not self.cacheable_core:
+        if self.gru_core:
             return self._act_cell_gru(lstm, feat, h, c, done)
         if feat.is_cuda and fused_lstm and feat.dtype == torch.float32 and h.shape[1] % 4 == 0:
             from . import fused
@@ -703,8 +748,8 @@ class A3C_Dueling(nn.Module):
         then knows the step's done flags and writes the next step's masked hidden rows). Only then is the one-GEMM LSTMCell
         store [features | k h_prev] built: with a separate env.step (RPF / Nav-less 'Full' ids, --rescale, --stack-frames > 1,
         NumpyVecEnv) nobody would write those hidden columns."""
-        if not self.cacheable_core:
-            return None
+        if self.gru_core:
+            return self._new_cache_gru(num_steps, states, env_fused) if self.cacheable_core else None
         p0, p1 = self.player0, self.player1
         ok = (states.is_cuda and states.dtype in (torch.float32, torch.uint8) and fused_lstm and not self.single
               and all(isinstance(p.encoder, CNN_maze) and p.encoder.small and p.encoder.use_fused
@@ -786,6 +831,47 @@ class A3C_Dueling(nn.Module):
             else:
                 c.emb = fa.weight.t() + fa.bias                    # row a = fc_action_tracker(one_hot(a))
                 c.emb_ih = c.emb @ p1.lstm.weight_ih.t()           # ... projected through W_ih: [n_act, 4R]
+        return c
+
+    def _new_cache_gru(self, num_steps, states, env_fused):
+        """new_cache for a GRU model with fused_gru_step: the cache exists ONLY in the one-GEMM env-fused form (at any N:
+        cat_gemm_min_rows is the LSTM's choice between two forms, a GRU has one) — fh_all [2, T+1, N, F+R] rows [features | k h_prev],
+        acts [2, T, N, 4R] = (r, z, n, q), h_all [2, T+1, N, R], c_all zero (a GRU's cx is never written; the bookkeeping launches
+        copy it as they find it), the step's constants W4 / b4 / E4 (gru_step_consts) under the LSTM cache's names w_cat / bsum /
+        emb_ih. Made with tensor ops here: the rollout's first launch only moves state. None in every other case — the Agent then
+        takes the path without a cache."""
+        from . import fused as _fz
+        p0, p1 = self.player0, self.player1
+        R, Fd = p0.lstm.hidden_size, p0.encoder.outdim
+        ok = (env_fused and states.is_cuda and states.dtype in (torch.float32, torch.uint8)
+              and all(isinstance(p.encoder, CNN_maze) and p.encoder.small and p.encoder.use_fused
+                      and p.encoder.conv1.in_channels == 1 for p in (p0, p1))
+              and states.shape[-1] == 13 and states.shape[-2] == 13 and self._gru_fused_static()
+              and self._env_fused_static(states.shape[0], R) and _fz.lt_available())
+        if not ok:
+            return None
+        T, N, dev = num_steps, states.shape[0], states.device
+        stack = states.shape[2]
+        c = RolloutCache()
+        c.gru = True
+        c.T, c.N, c.frames = T, N, [stack, 2 * stack if self.tat else stack]
+        c.y = [torch.empty((T, N * f, 512), device=dev) for f in c.frames]
+        c.fh_all = torch.empty((2, T + 1, N, Fd + R), device=dev)
+        c.hm_written = 0
+        c.f_all = c.fh_all[:, :T, :, :Fd]
+        c.f = [c.f_all[0], c.f_all[1]]
+        c.feat1 = c.pre_all = c.consts = None
+        c.has_wih_t = False
+        c.acts = torch.empty((2, T, N, 4 * R), device=dev)
+        c.h_all = torch.empty((2, T + 1, N, R), device=dev)
+        c.c_all = torch.zeros((2, T + 1, N, R), device=dev)
+        c.actions = torch.empty((T, 2, N), dtype=torch.int64, device=dev)
+        c.gates = torch.empty((2, N, 4 * R), device=dev)
+        if getattr(self, "_lt_ws", None) is None or self._lt_ws.device != dev:
+            self._lt_ws = torch.empty(32 << 20, dtype=torch.uint8, device=dev)
+        with torch.no_grad():
+            c.w_cat, b4, c.emb_ih = gru_step_consts((p0.lstm, p1.lstm), p1.fc_action_tracker if self.tat else None)
+        c.bsum = [b4[0], b4[1]]
         return c
 
     def _mfma_step_static(self, n, R):
@@ -894,6 +980,39 @@ class A3C_Dueling(nn.Module):
         # both players' stems in one launch, both hidden GEMMs in one bmm (neither depends on the tracker's action)
         ys = fused.stem_into2(x_in[0], p0.encoder, y[0], x_in[1], p1.encoder, y[1])
         R = h_prev.shape[-1]
+        if getattr(cache, "gru", False):
+            # the GRU cores' step (fused_gru_step), the only one a GRU cache knows: fc + ReLU into the feature columns of this
+            # step's [features | k h_prev] rows, ONE product against W4, then both cells + heads + draws + the env step as ONE
+            # launch (k_gru_step), which also writes the next step's masked hidden columns
+            self.env_stepped = False
+            if not (fh is not None and actions is not None and self._sampler._ordinal is not None and self.fused_sampling
+                    and self._env_fused_static(n, R)):
+                raise RuntimeError("a GRU rollout cache exists for the fused one-GEMM step only (new_cache decided so); the step at "
+                                   "hand would take another branch")
+            fh_t, fh_next = fh
+            if env_out is None and (fh_next is not None or greedy is not None):
+                raise RuntimeError("the GRU cores' cached step needs the env step inside its last launch: only the bootstrap step "
+                                   "runs without an env_out")
+            Fd = f_out[0].shape[-1]
+            if n <= self.pair_gemm_max_rows:
+                fused.pair_linear([ys[0].view(n, -1), ys[1].view(n, -1)], [p0.encoder.fc.weight, p1.encoder.fc.weight],
+                                  [fh_t[0][:, :Fd], fh_t[1][:, :Fd]], bias=[p0.encoder.fc.bias, p1.encoder.fc.bias], relu=True)
+            else:
+                for i, p in enumerate((p0, p1)):
+                    fused.linear_lt(ys[i].view(n, -1), p.encoder.fc.weight, fh_t[i][:, :Fd], bias=p.encoder.fc.bias, relu=True,
+                                    workspace=self._lt_ws)
+            fused.linear_lt(fh_t, cache.w_cat, cache.gates, workspace=self._lt_ws)
+            hm = [fh_next[0][:, Fd:], fh_next[1][:, Fd:]] if fh_next is not None else None
+            fused.gru_act_env_step(env_out[0] if env_out is not None else None, cache.gates, cache.bsum,
+                                   [fh_t[0][:, Fd:], fh_t[1][:, Fd:]], h_out, acts, self._sampler,
+                                   (p0.actor.actor_linear, p1.actor.actor_linear), actions, emb=cache.emb_ih,
+                                   env_out=env_out[1:] if env_out is not None else None, hm_out=hm, greedy=greedy is not None,
+                                   eval_out=greedy)
+            if hm is not None:
+                cache.hm_written = getattr(cache, "hm_written", 0) + 1
+            self.env_stepped = env_out is not None
+            self.env_step_fused_seen = self.env_step_fused_seen or self.env_stepped
+            return [actions[0], actions[1]]
         # the whole LSTMCell step (both GEMMs + cell) as one MFMA kernel per player (csrc/actor_step_hip.hip), the draw as
         # a second small launch; else hidden GEMMs as one bmm + per-player input GEMM + fused cell/head/draw kernel
         # (only from 3072 rows up: one wave tile per SIMD of the chip needs 4096 rows; at 1024 rows its 22 us per call lose to
@@ -1062,7 +1181,7 @@ class A3C_Dueling(nn.Module):
             pre = dict(bias=[cache.bsum[0], cache.bsum[1]], emb=cache.emb_ih if self.tat else None, emb_player=1,
                        act=actions_seq[:, :, 0])
         fold = None
-        if self.tat and (need is None or need[1]) and fused.embed_fold_ok(pre, cache.h_all, cache.c_all, keep, p1.fc_action_tracker):
+        if self.tat and not self.gru_core and (need is None or need[1]) and fused.embed_fold_ok(pre, cache.h_all, cache.c_all, keep, p1.fc_action_tracker):
             fold = p1.fc_action_tracker
         for i, p in enumerate((p0, p1)):
             enc = p.encoder
@@ -1086,6 +1205,8 @@ class A3C_Dueling(nn.Module):
         if getattr(cache, "fh_all", None) is not None and getattr(cache, "hm_written", 0) >= T:
             Fd = cache.f_all.shape[-1]
             hm = [cache.fh_all[i, :T, :, Fd:].view(T * N, -1) for i in range(2)]
+        if getattr(cache, "gru", False):     # (the node by core type: a GRU cache holds (r, z, n, q) and no cell state)
+            return fused.gru_sequence_cached([p0.lstm, p1.lstm], feats, keep, cache.h_all, cache.acts, need, hm=hm)
         acts = cache.pre_all if pre is not None else cache.acts
         return fused.lstm_sequence_cached([p0.lstm, p1.lstm], feats, keep, cache.h_all, cache.c_all, acts, need, hm=hm, pre=pre,
                                           fold=fold)

@@ -201,7 +201,7 @@ class Agent(object):
             return
         if obs0 is not None:
             self._buf[0][0].copy_(obs0)
-        if not getattr(self.model, "cacheable_core", True):
+        if getattr(self.model, "gru_core", False) or not getattr(self.model, "cacheable_core", True):
             # (the learner re-runs the recurrence from h0 / c0; under the pipelined schedule hxs / cxs are the carry, which the
             # next rollout overwrites while this rollout's learner may still be running: the GRU path keeps its own copy)
             self.h0, self.c0 = self.hxs.clone(), self.cxs.clone()

@@ -40,6 +40,9 @@ parser.add_argument('--aux', default='reward', help='auxiliary task: reward/none
 parser.add_argument('--graphed-eval', dest='graphed_eval', action='store_true',
                     help='run the episodes on the rollout kernels as replayed hipGraphs where the env allows it')
 parser.add_argument('--num-steps', type=int, default=20, metavar='NS', help='env steps per replayed graph (--graphed-eval)')
+parser.add_argument('--fused-gru', dest='fused_gru', action='store_true',
+                    help='maze-gru / tat-maze-gru: the fused one-GEMM step, which --graphed-eval needs for a GRU model '
+                         '(also ATR_FUSED_GRU=1)')
 
 if __name__ == '__main__':
     args = parser.parse_args()

@@ -62,6 +62,9 @@ parser.add_argument('--test-every', type=int, default=200, metavar='TI', help='t
 parser.add_argument('--graphed-eval', dest='graphed_eval', action='store_true',
                     help='evaluation rounds on the rollout kernels as replayed hipGraphs (greedy step with on-device episode '
                          'accounting) where the env allows it')
+parser.add_argument('--fused-gru', dest='fused_gru', action='store_true',
+                    help='maze-gru / tat-maze-gru: the cached rollout with the env-fused one-GEMM step (k_gru_step) and the graphed '
+                         'evaluator where they exist, instead of the path without a rollout cache (also ATR_FUSED_GRU=1)')
 parser.add_argument('--env', default='Track2D-BlockPartialPZR-v0', metavar='ENV', help='environment to train on')
 parser.add_argument('--env-base', default='Track2D-BlockPartialNav-v0', metavar='ENVB', help='environment to test on ')
 parser.add_argument('--optimizer', default='Adam', metavar='OPT', help='shares optimizer choice of Adam or RMSprop')

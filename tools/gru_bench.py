@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """What the GRU cores cost: the one-launch BPTT (atr_gru_bptt) against the per-step path, and a synchronous iteration of
-tat-maze-gru against tat-maze-lstm.
+tat-maze-gru against tat-maze-lstm; and the opt-in fused step (--fused-gru) against the path without a rollout cache.
 
     python tools/gru_bench.py                          # all variants, one fresh child process each, a table at the end
     python tools/gru_bench.py --one bptt fused         # one variant in this process: one JSON line
@@ -12,7 +12,12 @@ Variants, ONE per process (variants tried in one process pile up hardware queues
   iter tat-maze-gru | iter tat-maze-lstm
                                  train.GraphedIteration at 4096 envs: --warmup-steps env steps (>= 200), then --regions regions of
                                  --steps env steps (>= 200), median region as ms per iteration. The LSTM figure is the cached,
-                                 env-fused path's, the GRU's the path without a rollout cache: the GRU is expected to be slower."""
+                                 env-fused path's, the GRU's the path without a rollout cache: the GRU is expected to be slower.
+  fused sync-on | fused sync-off | fused pipe-on | fused pipe-off
+                                 tat-maze-gru at 4096 envs x 20 steps with the switch on (cached rollout, k_gru_step, the cached
+                                 learner) against off (today's path): a synchronous (train.GraphedIteration) and a pipelined
+                                 (train.PipelinedIteration) iteration, timed as `iter`. Whether the switch becomes the default is
+                                 decided from this output (profiles/r09_gru_fused_bench.txt once a run is recorded)."""
 import os
 import sys
 
@@ -28,7 +33,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-VARIANTS = (("bptt", "fused"), ("bptt", "per-step"), ("iter", "tat-maze-gru"), ("iter", "tat-maze-lstm"))
+VARIANTS = (("bptt", "fused"), ("bptt", "per-step"), ("iter", "tat-maze-gru"), ("iter", "tat-maze-lstm"),
+            ("fused", "sync-on"), ("fused", "sync-off"), ("fused", "pipe-on"), ("fused", "pipe-off"))
 
 
 def _median_regions(body, regions, sync):
@@ -90,6 +96,31 @@ def one_iter(net, a):
     player.env.close()
 
 
+def one_fused(which, a):
+    import torch
+    from active_tracking_rl_amd.train import GraphedIteration, PipelinedIteration, default_args, make_player
+    dev = torch.device("cuda:0")
+    schedule, switch = which.split("-")
+    args = default_args(num_envs=a.envs, network="tat-maze-gru", fused_gru=switch == "on")
+    T = args.num_steps
+    player, opt = make_player(args, dev)
+    sched = GraphedIteration(player, opt, args) if schedule == "sync" else PipelinedIteration(player, opt, args)
+
+    def run(n):
+        for _ in range(n):
+            sched.run()
+        sched.finish()
+        return n
+    run(a.warmup_steps // T)
+    med, lo, hi = _median_regions(lambda: run(a.steps // T), a.regions, lambda: torch.cuda.synchronize(dev))
+    agents = [player] if schedule == "sync" else sched.players
+    print(json.dumps(dict(kind="fused", variant=which, envs=a.envs, ms_per_iteration=round(med * 1e3, 5), ms_min=round(lo * 1e3, 5),
+                          ms_max=round(hi * 1e3, 5), regions=a.regions, steps=a.steps, warmup=a.warmup_steps,
+                          cached=all(p._cache is not None for p in agents),
+                          env_step_fused=bool(player.model.env_step_fused_seen))), flush=True)
+    player.env.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--one", nargs=2, metavar=("KIND", "VARIANT"))
@@ -103,7 +134,7 @@ def main():
     a = ap.parse_args()
     assert a.warmup_steps >= 200 and a.steps >= 200 and a.regions >= 5 and a.calls >= 10
     if a.one:
-        (one_bptt if a.one[0] == "bptt" else one_iter)(a.one[1], a)
+        dict(bptt=one_bptt, iter=one_iter, fused=one_fused)[a.one[0]](a.one[1], a)
         return
     rows = []
     for kind, variant in VARIANTS:
@@ -124,6 +155,12 @@ def main():
           "tat-maze-lstm %.4f ms (cached path), gru / lstm %.2f"
           % (a.envs, a.regions, a.steps, it["tat-maze-gru"]["ms_per_iteration"], it["tat-maze-lstm"]["ms_per_iteration"],
              it["tat-maze-gru"]["ms_per_iteration"] / it["tat-maze-lstm"]["ms_per_iteration"]))
+    f = {r["variant"]: r for r in rows if r["kind"] == "fused"}
+    for sched, name in (("sync", "synchronous"), ("pipe", "pipelined")):
+        on, off = f[sched + "-on"], f[sched + "-off"]
+        print("%s iteration of tat-maze-gru, %d envs: --fused-gru %.4f ms (cached %s), without %.4f ms (cached %s), on / off %.3f"
+              % (name, a.envs, on["ms_per_iteration"], on["cached"], off["ms_per_iteration"], off["cached"],
+                 on["ms_per_iteration"] / off["ms_per_iteration"]))
 
 
 if __name__ == "__main__":
