@@ -19,13 +19,15 @@ HEADERS = ["t2d_device.h", os.path.join("..", "..", "include", "track2d.h"),
            os.path.join("..", "..", "include", "atr_policy.h"), "atr_sample.h", "atr_cell.h",
            os.path.join("..", "..", "include", "track2d_np.h"), os.path.join("..", "..", "include", "atr_eval.h"),
            os.path.join("..", "..", "include", "atr_stats.h"), os.path.join("..", "..", "include", "atr_gru.h"),
-           os.path.join("..", "..", "include", "atr_gru_step.h")]
+           os.path.join("..", "..", "include", "atr_gru_step.h"), os.path.join("..", "..", "include", "atr_gru_sums.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wno-unused-result"]
 LDFLAGS = ["--offload-arch=gfx950", "-fPIC", "-shared", "-ldl"]
 # kernels that must not spill (source -> a part of their mangled names): the compiler's resource remarks are read when the source is
 # compiled, and scratch > 0 bytes per lane in one of them fails the build (k_gru_step: the LSTM forms of the step have none)
 NO_SCRATCH = {"track2d_hip.hip": "k_gru_step"}
+# ... and the learner's: every k_gru_bptt instantiation (W_hh lives in 96 of its VGPRs; the by-action sums add 12 accumulators)
+NO_SCRATCH_LEARNER = {"gru_hip.hip": "k_gru_bptt"}
 REMARKS = "-Rpass-analysis=kernel-resource-usage"
 
 
@@ -79,7 +81,8 @@ def build(force=False, verbose=False):
         cmd = [HIPCC] + CFLAGS + ["-c", os.path.join(CSRC, src), "-o", _obj(src)]
         if verbose:
             print(" ".join(cmd), flush=True)
-        if src not in NO_SCRATCH:
+        part = NO_SCRATCH.get(src) or NO_SCRATCH_LEARNER.get(src)
+        if part is None:
             subprocess.check_call(cmd)
             return
         r = subprocess.run(cmd + [REMARKS], stderr=subprocess.PIPE, text=True)
@@ -87,7 +90,7 @@ def build(force=False, verbose=False):
             sys.stderr.write(r.stderr)
             raise subprocess.CalledProcessError(r.returncode, cmd)
         sys.stderr.write("".join(l + "\n" for l in r.stderr.splitlines() if "warning:" in l))
-        bad = scratch_users(r.stderr, NO_SCRATCH[src])
+        bad = scratch_users(r.stderr, part)
         if bad:
             os.remove(_obj(src))
             raise RuntimeError("%s: scratch memory in %s" % (src, ", ".join("%s (%d bytes per lane)" % b for b in bad)))

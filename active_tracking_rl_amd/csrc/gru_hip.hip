@@ -16,6 +16,8 @@
 //                           registers of the thread that needs them at step t - 1. Per step: cell backward of the thread's 4
 //                           (row, unit) pairs, dG streamed out, the three hidden-side gradients parked in a double-buffered LDS
 //                           tile [16 x 384], ONE barrier, 96 MFMAs per wave with the next step's activations fetched under them.
+//   atr_gru_bptt_sums       the same launch, compiled with the by-action column sums of dG's input-side columns for the
+//                           tracker-aware target's embedding fold (include/atr_gru_sums.h); atr_gru_bptt's code has none of it.
 // The cell kernels are HBM-bound streaming kernels: one thread per 4 hidden units (16-byte accesses), grid-stride.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -164,9 +166,21 @@ struct GruBptt {
     float *dg;                 // + p * dg_ps + (t * N + n) * 4R (out)
     long long dg_ps;
     float *dh0;                // [P, N, R] (out)
+    // SUMS only: per row tile of player emb_player, the column sums of dG's INPUT-side columns (dr_pre, dz_pre, dn_pre) over the
+    // tile's rows and all T steps BY THE TRACKER'S ACTION of the row (int64, act + t * act_ts + n) — [tiles][4][3R]. S = their
+    // sum over the tiles is all the tracker-action embedding needs of the backward pass (include/atr_gru_sums.h: atr_gru_bptt_sums)
+    const long long *act;
+    long long act_ts;
+    int emb_player;
+    float *act_sums;
     int P, T, N;
 };
 
+// SUMS: the by-action column sums. The LDS tile holds (dr, dz, dq) — the MFMA's K — and not dn_pre, and a fourth LDS block for it
+// would pass the 64 KB default limit (2 x 16 x 516 floats), so the sums are taken in registers from the thread's own 4 (row, unit)
+// pairs: 4 actions x 3 gates = 12 accumulators of unit u (the kernel without them is at 194 of the 256 VGPRs __launch_bounds__(512,
+// 1) allows), then reduced ONCE over the 4 row groups q through the LDS tile after the last step.
+template <bool SUMS = false>
 __global__ __launch_bounds__(512, 1) void k_gru_bptt(GruBptt a)
 {
     extern __shared__ __attribute__((aligned(16))) float tileG[];      // [2][kGRows][kGLd]
@@ -198,6 +212,10 @@ __global__ __launch_bounds__(512, 1) void k_gru_bptt(GruBptt a)
     float dir[4] = {0.f, 0.f, 0.f, 0.f};       // dh_{t+1} z_{t+1}: the direct part of what step t + 1 sends into k_t h_t
     // staged inputs of one step (fetched one step ahead, under the MFMAs)
     float gr[4], gz[4], gn[4], gq[4], hpv[4], dhh[4], ko[4], ki[4];
+    // SUMS: the action of the thread's 4 rows (-1: a row past N, or not a move of the four-entry table — counted nowhere)
+    const bool sums = SUMS && p == a.emb_player;
+    int ai[4] = {-1, -1, -1, -1};
+    float sr[4] = {0.f, 0.f, 0.f, 0.f}, sz[4] = {0.f, 0.f, 0.f, 0.f}, sn[4] = {0.f, 0.f, 0.f, 0.f};      // [action]
 #define GRU_FETCH(t_)                                                                                                  \
     do {                                                                                                               \
         const int tt_ = (t_);                                                                                          \
@@ -209,6 +227,7 @@ __global__ __launch_bounds__(512, 1) void k_gru_bptt(GruBptt a)
             dhh[i] = dhp ? dhp[r_ * kGR + u] : 0.0f;                                                                   \
             ko[i] = a.keep[r_];                                                                                        \
             ki[i] = tt_ > 0 ? a.keep[r_ - a.N] : 1.0f;                                                                 \
+            if (SUMS && sums && ok[i]) ai[i] = (int)a.act[(size_t)tt_ * a.act_ts + rows[i]];                           \
         }                                                                                                              \
     } while (0)
     GRU_FETCH(a.T - 1);
@@ -229,6 +248,13 @@ __global__ __launch_bounds__(512, 1) void k_gru_bptt(GruBptt a)
                 float *o = dg + ((size_t)t * a.N + rows[i]) * kGW + u;
                 __builtin_nontemporal_store(g.dr, o); __builtin_nontemporal_store(g.dz, o + kGR);       // streamed out: the
                 __builtin_nontemporal_store(g.dn, o + 2 * kGR); __builtin_nontemporal_store(g.dq, o + 3 * kGR);  // GEMMs read dG later
+            }
+            if (SUMS && sums) {                            // (fmaf(1, v, s) = s + v, fmaf(0, v, s) = s: exact either way)
+#pragma unroll
+                for (int c = 0; c < 4; c++) {
+                    const float m = ai[i] == c ? 1.0f : 0.0f;
+                    sr[c] = fmaf(m, g.dr, sr[c]); sz[c] = fmaf(m, g.dz, sz[c]); sn[c] = fmaf(m, g.dn, sn[c]);
+                }
             }
         }
         __syncthreads();                                   // the tile of step t is complete (the other buffer: step t + 1's
@@ -264,6 +290,24 @@ __global__ __launch_bounds__(512, 1) void k_gru_bptt(GruBptt a)
         acc += acc2;
     }
 #undef GRU_FETCH
+    if (SUMS && sums) {
+        // ---- the 4 row groups' partial sums of unit u meet in LDS: red [q][action][gate][R] = 6144 floats, summed in the fixed order
+        // q = 0..3; thread tid writes columns tid, tid + 512, tid + 1024 of the tile's [4][3R] block (all of it, zeros included)
+        __syncthreads();                                   // every wave's MFMA reads of the last step's tile are done
+        float *red = tileG;
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+            float *o = red + (size_t)((q * 4 + c) * 3) * kGR + u;
+            o[0] = sr[c]; o[kGR] = sz[c]; o[2 * kGR] = sn[c];
+        }
+        __syncthreads();
+        float *out = a.act_sums + (size_t)rt * 4 * kGK;
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            const int o = tid + 512 * k;                   // = action * 3R + gate * R + unit: red's own order within one q
+            out[o] = ((red[o] + red[4 * kGK + o]) + red[2 * 4 * kGK + o]) + red[3 * 4 * kGK + o];
+        }
+    }
     // ---- gradient into the rollout's initial hidden state (slot 0 comes masked: no k here)
 #pragma unroll
     for (int i = 0; i < 4; i++)
@@ -305,19 +349,45 @@ extern "C" int atr_gru_cell_backward(const float *dh_out, long long dh_pstride, 
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
-extern "C" int atr_gru_bptt(const float *dh0_heads, const float *dh1_heads, const float *keep, const float *acts,
-                            long long acts_pstride, const float *h_all, long long h_pstride, const float *whh0,
-                            const float *whh1, float *dg, long long dg_pstride, float *dh_init, int P, int T, int N, int R,
-                            void *stream)
+static int gru_bptt_launch(const float *dh0_heads, const float *dh1_heads, const float *keep, const float *acts,
+                           long long acts_pstride, const float *h_all, long long h_pstride, const float *whh0,
+                           const float *whh1, float *dg, long long dg_pstride, float *dh_init, int emb_player,
+                           const long long *act_tracker, long long act_tstride, float *act_sums, int P, int T, int N, int R,
+                           void *stream)
 {
     if (!keep || !acts || !h_all || !whh0 || !dg || !dh_init || P < 1 || P > 2 || (P == 2 && !whh1) || T < 1 || N < 1 || R != kGR)
         return -1;
     GruBptt a;
     a.dh[0] = dh0_heads; a.dh[1] = dh1_heads; a.keep = keep; a.acts = acts; a.acts_ps = acts_pstride; a.h_all = h_all;
     a.h_ps = h_pstride; a.whh[0] = whh0; a.whh[1] = whh1; a.dg = dg; a.dg_ps = dg_pstride; a.dh0 = dh_init;
+    a.act = act_tracker; a.act_ts = act_tstride; a.emb_player = emb_player; a.act_sums = act_sums;
     a.P = P; a.T = T; a.N = N;
     const size_t lds = (size_t)2 * kGRows * kGLd * sizeof(float);          // 49 664 bytes: under the 64 KB default limit
     const unsigned grid = (unsigned)(P * ((N + kGRows - 1) / kGRows));
-    hipLaunchKernelGGL(k_gru_bptt, dim3(grid), dim3(512), lds, (hipStream_t)stream, a);
+    if (act_sums) hipLaunchKernelGGL(k_gru_bptt<true>, dim3(grid), dim3(512), lds, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(k_gru_bptt<false>, dim3(grid), dim3(512), lds, (hipStream_t)stream, a);
     return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+extern "C" int atr_gru_bptt(const float *dh0_heads, const float *dh1_heads, const float *keep, const float *acts,
+                            long long acts_pstride, const float *h_all, long long h_pstride, const float *whh0,
+                            const float *whh1, float *dg, long long dg_pstride, float *dh_init, int P, int T, int N, int R,
+                            void *stream)
+{
+    return gru_bptt_launch(dh0_heads, dh1_heads, keep, acts, acts_pstride, h_all, h_pstride, whh0, whh1, dg, dg_pstride, dh_init,
+                           -1, nullptr, 0, nullptr, P, T, N, R, stream);
+}
+
+extern "C" long long atr_gru_bptt_act_sums_floats(int N) { return (long long)((N + kGRows - 1) / kGRows) * 4 * kGK; }
+
+extern "C" int atr_gru_bptt_sums(const float *dh0_heads, const float *dh1_heads, const float *keep, const float *acts,
+                                 long long acts_pstride, const float *h_all, long long h_pstride, const float *whh0,
+                                 const float *whh1, float *dg, long long dg_pstride, float *dh_init, int emb_player, int n_act,
+                                 const long long *act_tracker, long long act_tstride, float *act_sums, int P, int T, int N, int R,
+                                 void *stream)
+{
+    // (the by-action sums are built for the four-move action table)
+    if (!act_sums || !act_tracker || n_act != 4 || emb_player < 0 || emb_player >= P) return -1;
+    return gru_bptt_launch(dh0_heads, dh1_heads, keep, acts, acts_pstride, h_all, h_pstride, whh0, whh1, dg, dg_pstride, dh_init,
+                           emb_player, act_tracker, act_tstride, act_sums, P, T, N, R, stream);
 }

@@ -183,6 +183,13 @@ GRU_PROTOTYPES = {
     "atr_gru_bptt": (C.c_int, [C.c_void_p] * 4 + [C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p,
                                C.c_longlong, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
 }
+# the GRU learner's BPTT with the by-action column sums, include/atr_gru_sums.h (held to the header by tests/test_gru_learner_cpu.py)
+GRU_SUMS_PROTOTYPES = {
+    "atr_gru_bptt_act_sums_floats": (C.c_longlong, [C.c_int]),
+    # (atr_gru_bptt's arguments up to dh_init, then emb_player, n_act, act_tracker, act_tstride, act_sums, P, T, N, R, stream)
+    "atr_gru_bptt_sums": (C.c_int, GRU_PROTOTYPES["atr_gru_bptt"][1][:12] + [C.c_int, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p,
+                                                                            C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+}
 # the GRU cores' fused rollout step, include/atr_gru_step.h (opt-in: --fused-gru; held to the header by tests/test_gru_fused_cpu.py)
 GRU_STEP_PROTOTYPES = {
     "atr_gru_act_env_step": (C.c_int, [C.c_void_p, C.POINTER(ActStepArgs), C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p,
@@ -212,7 +219,7 @@ def lib():
     if _lib is None:
         L = vec_env.load_library()
         for name, (restype, argtypes, *value) in (list(ATR_PROTOTYPES.items()) + list(GRU_PROTOTYPES.items())
-                                                  + list(GRU_STEP_PROTOTYPES.items())):
+                                                  + list(GRU_SUMS_PROTOTYPES.items()) + list(GRU_STEP_PROTOTYPES.items())):
             f = getattr(L, name)
             f.restype, f.argtypes = restype, argtypes
             if restype is C.c_int and not value:
@@ -872,12 +879,22 @@ def _hidden_cols(x, R):
     return torch.cat([x[..., :2 * R], x[..., 3 * R:]], -1)
 
 
-def _gru_bptt(whh, keep, h_all, acts, dhs, hm=None):
+def _fused_gru_bptt_ok(h_all, *stores):
+    """Whether the one-launch GRU BPTT (atr_gru_bptt) can run: switched on, R = 128, on the GPU, the stores contiguous."""
+    return bool(use_fused_gru_bptt and h_all.shape[-1] == 128 and h_all.is_cuda
+                and all(t.is_contiguous() for t in (h_all,) + stores))
+
+
+def _gru_bptt(whh, keep, h_all, acts, dhs, hm=None, want_dw=True, sums=None):
     """Back-propagation through time over a GRU recurrence's stored activations: whh [P,R,3R], keep [T,N], h_all [P,T+1,N,R],
     acts [P,T,N,4R] = (r, z, n, q), dhs = per-player dL/dh_seq [T,N,R] (None = zero). Returns dG [P, T*N, 4R] = (dr_pre, dz_pre,
-    dn_pre, dn_pre r) — columns 0:3R are dL/d ig —, dL/dh0 [P,N,R], dL/dW_hh^T [P,R,3R] and dL/db_hh [P,3R].
+    dn_pre, dn_pre r) — columns 0:3R are dL/d ig —, dL/dh0 [P,N,R], dL/dW_hh^T [P,R,3R] and dL/db_hh [P,3R] (both None when
+    not want_dw: the caller registers those products with the grouped weight-gradient launch).
     hm: per player the masked rows k_{t-1} h_{t-1} [T*N,R] where the rollout stored them (row-strided views are fine): dW_hh
-    contracts them as they are."""
+    contracts them as they are.
+    sums: None, or dict(emb_player, act = [T, N] int64 view of the tracker's actions) — the one-launch kernel then also leaves,
+    as sums['act_sums'], the column sums of dG[..., 0:3R] of player emb_player by the row's tracker action (atr_gru_bptt_sums:
+    what embed_fold reads with J = 3R); None there when the per-step path ran."""
     L = lib()
     P, T1, N, R = h_all.shape
     T = T1 - 1
@@ -887,11 +904,21 @@ def _gru_bptt(whh, keep, h_all, acts, dhs, hm=None):
     st = _stream(h_all)
     ps, pa, step, astep = (T + 1) * N * R, T * N * 4 * R, N * R * 4, N * 4 * R * 4
     whh_nn = whh.transpose(1, 2)                                                  # [P,3R,R]: nn.GRUCell's weight_hh
-    if use_fused_gru_bptt and R == 128 and h_all.is_cuda and all(t.is_contiguous() for t in (h_all, acts, keep)):
+    if sums is not None:
+        sums["act_sums"] = None
+    if _fused_gru_bptt_ok(h_all, acts, keep):
         whh_nn = whh_nn.contiguous()
         dh_c = [d.contiguous() if d is not None else None for d in dhs]
-        L.atr_gru_bptt(_pn(dh_c[0]), _pn(dh_c[1]) if P > 1 else None, _p(keep), _p(acts), pa, _p(h_all), ps, _p(whh_nn[0]),
-                       _p(whh_nn[1]) if P > 1 else None, _p(dG), pa, _p(dhn), P, T, N, R, st)
+        if sums is not None:
+            act, ep = sums["act"], int(sums["emb_player"])
+            assert act.dtype == torch.int64 and act.shape == (T, N) and act.stride(1) == 1 and 0 <= ep < P
+            sums["act_sums"] = torch.empty(L.atr_gru_bptt_act_sums_floats(N), dtype=torch.float32, device=dev)
+            L.atr_gru_bptt_sums(_pn(dh_c[0]), _pn(dh_c[1]) if P > 1 else None, _p(keep), _p(acts), pa, _p(h_all), ps,
+                                _p(whh_nn[0]), _p(whh_nn[1]) if P > 1 else None, _p(dG), pa, _p(dhn), ep, 4, _p(act),
+                                act.stride(0), _p(sums["act_sums"]), P, T, N, R, st)
+        else:
+            L.atr_gru_bptt(_pn(dh_c[0]), _pn(dh_c[1]) if P > 1 else None, _p(keep), _p(acts), pa, _p(h_all), ps, _p(whh_nn[0]),
+                           _p(whh_nn[1]) if P > 1 else None, _p(dG), pa, _p(dhn), P, T, N, R, st)
     else:
         dhs = [torch.zeros((T, N, R), dtype=torch.float32, device=dev) if d is None else d.contiguous() for d in dhs]
         pd = (dhs[1].data_ptr() - dhs[0].data_ptr()) // 4 if P > 1 else 0          # player stride between the two grads
@@ -905,6 +932,8 @@ def _gru_bptt(whh, keep, h_all, acts, dhs, hm=None):
             dhn.baddbmm_(dG[:, t], w4)                                            # + dG_t W_hh: the gradient into k h_{t-1}
     # W_hh: sum_t (k_{t-1} h_{t-1})^T dG_t[hidden columns] as one GEMM per player over all T*N rows; b_hh: their column sums
     dG = dG.view(P, T * N, 4 * R)
+    if not want_dw:
+        return dG, dhn, None, None
     if hm is not None:
         dwhh = _hidden_cols(torch.stack([gemm_tn(hm[p], dG[p]) for p in range(P)], 0), R)
     else:
@@ -917,17 +946,27 @@ def _gru_bptt(whh, keep, h_all, acts, dhs, hm=None):
 class _GruSeqCached(torch.autograd.Function):
     """_LstmSeqCached for the GRU cores (--fused-gru): the input projection + masked recurrence of both players as an autograd node
     whose forward the rollout already evaluated step by step (gru_act_env_step, same weights): h_all [P,T+1,N,R] and acts
-    [P,T,N,4R] = (r, z, n, q) hold every step. Inputs: per-player features [T*N,F] and GRUCell parameters; output: per-player
-    h_seq [T,N,R]. Backward: _gru_bptt on the stores, then per trained player dfeat = dG[:, :3R] W_ih, dW_ih / d b_ih from one
-    gemm_tn over dG's rows (its fourth column block belongs to the hidden side: d b_hh = the hidden columns' sums), dW_hh from
-    the stored masked rows where the rollout wrote them all. No grouped launch, no embedding fold."""
+    [P,T,N,4R] = (r, z, n, q) hold every step. Inputs: per-player features [T*N,F] and GRUCell parameters (+ fc_action_tracker's
+    weight and bias when the tracker-action embedding is folded: the target's features are then its RAW fc features); output:
+    per-player h_seq [T,N,R]. Backward: _gru_bptt on the stores, then per trained player dfeat = dG[:, :3R] W_ih and three
+    weight-gradient products over dG's column blocks (include/atr_gru.h):
+        dW_ih          = dG[:, 0:3R]^T f         column sums -> d b_ih
+        dW_hh[0:2R]    = dG[:, 0:2R]^T (k h)     column sums -> d b_hh[0:2R]
+        dW_hh[2R:3R]   = dG[:, 3R:4R]^T (k h)    column sums -> d b_hh[2R:3R]
+    registered with the grouped launch of the backward pass (DeferredWeightGrads: a player joins with all three or with none)
+    under _LstmSeqCached's conditions, computed on the spot otherwise. Folded, the embedding's share comes from the by-action
+    column sums of dG the BPTT launch leaves (embed_fold with J = 3R): dW_ih += S^T E, d fc_action_tracker = (S W_ih)^T."""
 
     @staticmethod
     def forward(ctx, keep, h_all, acts, opts, *fw):
         P = h_all.shape[0]
-        need, hm = opts
-        ctx.save_for_backward(keep.contiguous(), h_all, acts, *fw[:3 * P], *(hm if hm is not None else ()))
-        ctx.P, ctx.has_hm = P, hm is not None
+        need, hm, fold = opts                     # fold: None or dict(emb_player, act) — see gru_sequence_cached
+        ctx.fold = fold is not None
+        assert len(fw) == 5 * P + (2 if ctx.fold else 0)
+        ctx.save_for_backward(keep.contiguous(), h_all, acts, *fw, *(hm if hm is not None else ()),
+                              *((fold["act"],) if ctx.fold else ()))
+        ctx.P, ctx.has_hm, ctx.n_fw = P, hm is not None, len(fw)
+        ctx.emb_player = int(fold["emb_player"]) if ctx.fold else -1
         ctx.need = tuple(bool(x) for x in need) if need is not None else (True,) * P
         return tuple(h_all[p, 1:] for p in range(P))
 
@@ -935,30 +974,93 @@ class _GruSeqCached(torch.autograd.Function):
     def backward(ctx, *dhs):
         P = ctx.P
         keep, h_all, acts = ctx.saved_tensors[:3]
-        feats, wih, whh_nn = (ctx.saved_tensors[3 + i * P:3 + (i + 1) * P] for i in range(3))
-        hm = ctx.saved_tensors[3 + 3 * P:] if ctx.has_hm else None
-        R = h_all.shape[-1]
+        feats, wih, whh_nn, bih, bhh = (ctx.saved_tensors[3 + i * P:3 + (i + 1) * P] for i in range(5))
+        rest = ctx.saved_tensors[3 + ctx.n_fw:]
+        hm = rest[:P] if ctx.has_hm else None
+        fa_w, fa_b = ctx.saved_tensors[3 + 5 * P:5 + 5 * P] if ctx.fold else (None, None)
+        act = rest[-1] if ctx.fold else None
+        T, N, R = h_all.shape[1] - 1, h_all.shape[2], h_all.shape[3]
         dfeat, dwih, dwhh, dbih, dbhh = ([None] * P for _ in range(5))
+        dfa = (None, None)
+        q = _deferred
         # (a player the loss does not train — train-mode 0 / 1 — has none of its recurrence back-propagated)
         groups = [list(range(P))] if all(ctx.need) else [[p] for p in range(P) if ctx.need[p]]
         for grp in groups:
             a, b = grp[0], grp[-1] + 1
+            defer = q is not None and _fused_gru_bptt_ok(h_all, acts, keep) and T * N >= 4096
+            fold_p = ctx.emb_player if (ctx.fold and a <= ctx.emb_player < b) else -1
+            sums = dict(emb_player=fold_p - a, act=act) if fold_p >= 0 else None      # (the player's index within the group)
             whh = torch.stack([w.t() for w in whh_nn[a:b]], 0)
-            dG, _, dwhh_t, dbhh_g = _gru_bptt(whh, keep, h_all[a:b], acts[a:b], dhs[a:b], hm=hm[a:b] if hm is not None else None)
+            dG, _, dwhh_t, dbhh_g = _gru_bptt(whh, keep, h_all[a:b], acts[a:b], dhs[a:b], hm=hm[a:b] if hm is not None else None,
+                                              want_dw=not defer, sums=sums)
+            if fold_p >= 0 and sums["act_sums"] is None:
+                raise RuntimeError("folded tracker-action embedding: the BPTT launch did not return the by-action sums of dG")
             for i, p in enumerate(grp):
-                dfeat[p] = dG[i][:, :3 * R] @ wih[p]
-                dw, cs = gemm_tn(dG[i], feats[p], colsum=True)
+                dGi = dG[i]
+                dfeat[p] = dGi[:, :3 * R] @ wih[p]
+                if p == fold_p:
+                    # (feats[p] are the RAW fc features: dW_ih's product misses S^T E, added by embed_fold once the product is there)
+                    fold_args = (sums["act_sums"], fa_w, fa_b, wih[p])
+                    dfa = (torch.empty_like(fa_w), torch.empty_like(fa_b))
+                if defer:
+                    # k h rows stored by the rollout: nothing to mask, and the hidden columns' sums are d b_hh. Otherwise the
+                    # mask on h_{t-1} is keep[t-1] = the keep array shifted by one step of N rows, applied to dG's rows on
+                    # their way into the kernel — the column sums would carry it too, so d b_hh is summed here
+                    if hm is not None:
+                        x2h, rs, bh = hm[p], {}, (bhh[p],)
+                    else:
+                        x2h, rs, bh = h_all[p, :T].reshape(T * N, R), dict(row_scale=keep, shift=N), ()
+                    r = q.add_all([dict(x1=dGi[:, :3 * R], x2=feats[p], weight=wih[p], biases=(bih[p],)),
+                                   dict(x1=dGi[:, :2 * R], x2=x2h, weight=whh_nn[p], biases=bh, rows=(0, 2 * R), **rs),
+                                   dict(x1=dGi[:, 3 * R:], x2=x2h, weight=whh_nn[p], biases=bh, rows=(2 * R, 3 * R), **rs)])
+                    if r is not None:
+                        dwih[p], dbih[p] = r[0][0], r[0][1][0]
+                        dwhh[p] = r[1][0]
+                        dbhh[p] = r[1][1][0] if bh else _hidden_cols(dGi.sum(0), R)
+                        if p == fold_p:          # (the slice is filled by the grouped launch at flush(): the fold follows it)
+                            q.after.append(lambda fa_=fold_args, dw_=dwih[p], out_=dfa: embed_fold(*fa_, dw_, *out_))
+                        continue
+                    # (no room in the group, or a product that does not fit it: this player's products on the spot)
+                    if hm is not None:
+                        dwhh[p] = _hidden_cols(gemm_tn(hm[p], dGi), R).t()
+                    else:
+                        kprev = _keep_prev(keep).reshape(T * N)
+                        dwhh[p] = _hidden_cols(gemm_tn(h_all[p, :T].reshape(T * N, R), dGi, row_scale=kprev), R).t()
+                    dbhh[p] = _hidden_cols(dGi.sum(0), R)
+                else:
+                    dwhh[p], dbhh[p] = dwhh_t[i].t(), dbhh_g[i]
+                dw, cs = gemm_tn(dGi, feats[p], colsum=True)
                 dwih[p], dbih[p] = dw[:3 * R], cs[:3 * R]
-                dwhh[p], dbhh[p] = dwhh_t[i].t(), dbhh_g[i]
-        return (None, None, None, None) + tuple(dfeat) + tuple(dwih) + tuple(dwhh) + tuple(dbih) + tuple(dbhh)
+                if p == fold_p:
+                    dwih[p] = dwih[p].contiguous()
+                    embed_fold(*fold_args, dwih[p], *dfa)
+        if ctx.fold and ctx.need[ctx.emb_player] and dfa[0] is None:
+            raise RuntimeError("folded tracker-action embedding: no group of the backward pass produced its gradients")
+        out = (None, None, None, None) + tuple(dfeat) + tuple(dwih) + tuple(dwhh) + tuple(dbih) + tuple(dbhh)
+        return out + (tuple(dfa) if ctx.fold else ())
 
 
-def gru_sequence_cached(cells, feats, keep, h_all, acts, need=None, hm=None):
+def gru_sequence_cached(cells, feats, keep, h_all, acts, need=None, hm=None, fold=None, act=None, emb_player=1):
     """lstm_sequence_cached for nn.GRUCells: feats per-player [T*N,F] (with grad), the rollout's stores h_all / acts = (r, z, n,
-    q); need per player as there; hm per player the masked previous hidden rows [T*N,R] when the rollout stored every one."""
+    q); need per player as there; hm per player the masked previous hidden rows [T*N,R] when the rollout stored every one.
+    fold = the tracker-aware player's fc_action_tracker (see gru_embed_fold_ok): feats[emb_player] are then its RAW fc features
+    (no f + E[a] materialised) and the embedding's gradients come from this node; act = the [T, N] int64 view of the tracker's
+    actions (one player's column of the rollout's [T, players, N] store, read in place)."""
     args = list(feats) + [l.weight_ih for l in cells] + [l.weight_hh for l in cells] + [l.bias_ih for l in cells] + \
         [l.bias_hh for l in cells]
-    return _GruSeqCached.apply(keep, h_all, acts, (need, hm), *args)
+    fold_info = None
+    if fold is not None:
+        assert act is not None and act.dtype == torch.int64 and act.stride(1) == 1
+        args += [fold.weight, fold.bias]
+        fold_info = dict(emb_player=emb_player, act=act)
+    return _GruSeqCached.apply(keep, h_all, acts, (need, hm, fold_info), *args)
+
+
+def gru_embed_fold_ok(h_all, acts, keep, fa):
+    """Whether gru_sequence_cached can fold the tracker-action embedding (the one-launch GRU BPTT, the four-move action table,
+    parameters as the kernels read them)."""
+    return bool(fold_embedding and _fused_gru_bptt_ok(h_all, acts, keep.contiguous()) and fa.weight.shape[1] == 4
+                and fa.weight.is_contiguous() and fa.weight.data_ptr() % 16 == 0)
 
 
 class _LstmSeqCached(torch.autograd.Function):
@@ -1059,8 +1161,8 @@ class _LstmSeqCached(torch.autograd.Function):
 @torch.no_grad()
 def embed_fold(act_sums, fa_w, fa_b, wih, dwih, dfa_w, dfa_b):
     """The tracker-action embedding's share of the target's backward pass from the by-action column sums of dG (atr_embed_fold):
-    dwih [4R, C] += S^T E in place, dfa_w [C, 4] / dfa_b [C] = the gradients of fc_action_tracker. act_sums: what
-    atr_lstm_bptt_pre2 left per row tile."""
+    dwih [J, C] += S^T E in place, dfa_w [C, 4] / dfa_b [C] = the gradients of fc_action_tracker. act_sums: what
+    atr_lstm_bptt_pre2 (J = 4R) or atr_gru_bptt_sums (J = 3R) left per row tile."""
     J, Cc = wih.shape
     assert fa_w.shape == (Cc, 4) and fa_w.is_contiguous() and fa_b.is_contiguous() and wih.is_contiguous() and dwih.is_contiguous()
     assert dwih.shape == (J, Cc) and act_sums.numel() % (4 * J) == 0
@@ -1609,25 +1711,56 @@ class DeferredWeightGrads(object):
     def view(self, prm):
         return self.views.get(prm.data_ptr()) if prm is not None else None
 
-    def add(self, x1, x2, weight, biases=(), row_scale=None, shift=0):
-        """Register dW = x1^T x2 -> `weight`'s gradient slice, colsum(x1) -> the slices of `biases` (<= 2). Returns
-        (dW view, [bias views]) or None when this product cannot join the group (shape class, parameter not in the bucket, a
-        different K, group full): the caller then computes it on the spot."""
+    def _problem(self, x1, x2, weight, biases=(), row_scale=None, shift=0, rows=None):
+        """The record of dW = x1^T x2 as add() describes it, or None when the product cannot join a group with K rows."""
         K, M = x1.shape
         N = x2.shape[1]
-        dst = self.view(weight)
-        bv = [self.view(b) for b in biases]
-        if (dst is None or any(v is None for v in bv) or len(bv) > 2 or len(self.problems) >= self.MAX
-                or (self.K is not None and K != self.K) or K < 4096 or M % 128 or N % 128
-                or not (x1.is_cuda and x1.dtype == torch.float32 and x2.dtype == torch.float32
-                        and x1.is_contiguous() and x2.stride(1) == 1 and x2.stride(0) >= N and x2.stride(0) % 4 == 0
-                        and x2.data_ptr() % 16 == 0)
-                or tuple(dst.shape) != (M, N) or (row_scale is not None and not row_scale.is_contiguous())):
+        whole = self.view(weight)
+        bw = [self.view(b) for b in biases]
+        if whole is None or any(v is None for v in bw) or len(bw) > 2:
             return None
-        self.K = K
-        self.problems.append((x1, x2, dst, row_scale, int(shift), bv, M, N))
-        self.registered.update(v.data_ptr() for v in [dst] + bv)
-        return dst, bv
+        dst, bv = whole, bw
+        if rows is not None:
+            if whole.dim() != 2 or not (0 <= rows[0] < rows[1] <= whole.shape[0]):
+                return None
+            dst, bv = whole[rows[0]:rows[1]], [v[rows[0]:rows[1]] for v in bw]
+        if ((self.K is not None and K != self.K) or K < 4096 or M % 128 or N % 128
+                or not (x1.is_cuda and x1.dtype == torch.float32 and x2.dtype == torch.float32
+                        and x1.stride(1) == 1 and x1.stride(0) >= M and x1.stride(0) % 4 == 0 and x1.data_ptr() % 16 == 0
+                        and x2.stride(1) == 1 and x2.stride(0) >= N and x2.stride(0) % 4 == 0
+                        and x2.data_ptr() % 16 == 0)
+                or tuple(dst.shape) != (M, N) or any(tuple(v.shape) != (M,) for v in bv)
+                or (row_scale is not None and not row_scale.is_contiguous())):
+            return None
+        return (x1, x2, dst, row_scale, int(shift), bv, M, N), (whole, bw)
+
+    def _commit(self, rec):
+        prob, (whole, bw) = rec
+        self.K = prob[0].shape[0]
+        self.problems.append(prob)
+        self.registered.update(v.data_ptr() for v in [whole] + bw)       # (check(): what autograd gets back is the WHOLE slice)
+        return whole, bw
+
+    def add(self, x1, x2, weight, biases=(), row_scale=None, shift=0, rows=None):
+        """Register dW = x1^T x2 -> `weight`'s gradient slice, colsum(x1) -> the slices of `biases` (<= 2). x1 may be a column
+        block of a wider row-major tensor (16-byte aligned, row stride a multiple of 4 floats). rows = (r0, r1): the product is
+        rows r0:r1 of the weight's gradient and its column sums rows r0:r1 of the biases' (the caller registers the other rows
+        too). Returns (the parameter's WHOLE dW view, [whole bias views]) or None when this product cannot join the group
+        (shape class, parameter not in the bucket, a different K, group full): the caller then computes it on the spot."""
+        if len(self.problems) >= self.MAX:
+            return None
+        rec = self._problem(x1, x2, weight, biases, row_scale, shift, rows)
+        return self._commit(rec) if rec is not None else None
+
+    def add_all(self, products):
+        """add() for products that join the group together or not at all (a list of add()'s keyword arguments): the list of
+        their results, or None — the room is checked first, nothing is registered for a group that is merely full."""
+        if len(self.problems) + len(products) > self.MAX:
+            return None
+        recs = [self._problem(**kw) for kw in products]
+        if any(rec is None for rec in recs) or len(set(rec[0][0].shape[0] for rec in recs)) > 1:
+            return None
+        return [self._commit(rec) for rec in recs]
 
     def check(self, grads):
         """The gradients autograd handed back for the registered parameters must BE the bucket slices the nodes returned (a
@@ -1650,7 +1783,7 @@ class DeferredWeightGrads(object):
             arr[q].colsum0 = bv[0].data_ptr() if len(bv) > 0 else None
             arr[q].colsum1 = bv[1].data_ptr() if len(bv) > 1 else None
             arr[q].M, arr[q].N = M, N
-            arr[q].ld1, arr[q].ld2 = M, x2.stride(0)
+            arr[q].ld1, arr[q].ld2 = x1.stride(0), x2.stride(0)
         L = lib()
         x0 = self.problems[0][0]
         ws = torch.empty(L.atr_gemm_tn_grouped_workspace_floats(arr, n, self.K), dtype=torch.float32, device=x0.device)

@@ -1181,8 +1181,12 @@ class A3C_Dueling(nn.Module):
             pre = dict(bias=[cache.bsum[0], cache.bsum[1]], emb=cache.emb_ih if self.tat else None, emb_player=1,
                        act=actions_seq[:, :, 0])
         fold = None
-        if self.tat and not self.gru_core and (need is None or need[1]) and fused.embed_fold_ok(pre, cache.h_all, cache.c_all, keep, p1.fc_action_tracker):
-            fold = p1.fc_action_tracker
+        if self.tat and (need is None or need[1]):
+            if getattr(cache, "gru", False):     # (a GRU cache holds activated gates: the fold needs only the by-action sums)
+                if fused.gru_embed_fold_ok(cache.h_all, cache.acts, keep, p1.fc_action_tracker):
+                    fold = p1.fc_action_tracker
+            elif not self.gru_core and fused.embed_fold_ok(pre, cache.h_all, cache.c_all, keep, p1.fc_action_tracker):
+                fold = p1.fc_action_tracker
         for i, p in enumerate((p0, p1)):
             enc = p.encoder
             y = fused.stem_cached(x_in[i], cache.y[i].view(-1, 512), enc.conv1, enc.conv2)
@@ -1206,7 +1210,8 @@ class A3C_Dueling(nn.Module):
             Fd = cache.f_all.shape[-1]
             hm = [cache.fh_all[i, :T, :, Fd:].view(T * N, -1) for i in range(2)]
         if getattr(cache, "gru", False):     # (the node by core type: a GRU cache holds (r, z, n, q) and no cell state)
-            return fused.gru_sequence_cached([p0.lstm, p1.lstm], feats, keep, cache.h_all, cache.acts, need, hm=hm)
+            return fused.gru_sequence_cached([p0.lstm, p1.lstm], feats, keep, cache.h_all, cache.acts, need, hm=hm, fold=fold,
+                                             act=actions_seq[:, :, 0] if fold is not None else None)
         acts = cache.pre_all if pre is not None else cache.acts
         return fused.lstm_sequence_cached([p0.lstm, p1.lstm], feats, keep, cache.h_all, cache.c_all, acts, need, hm=hm, pre=pre,
                                           fold=fold)

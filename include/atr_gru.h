@@ -49,6 +49,10 @@ int atr_gru_bptt(const float *dh0_heads, const float *dh1_heads, const float *ke
                  const float *h_all, long long h_pstride, const float *whh0, const float *whh1, float *dg,
                  long long dg_pstride, float *dh_init, int P, int T, int N, int R, void *stream);
 
+/* atr_gru_bptt with the by-action column sums of dG the tracker-action embedding's fold needs (atr_gru_bptt_sums,
+ * atr_gru_bptt_act_sums_floats): declared in atr_gru_sums.h, which this header brings along. */
+#include "atr_gru_sums.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,7 +17,13 @@ Variants, ONE per process (variants tried in one process pile up hardware queues
                                  tat-maze-gru at 4096 envs x 20 steps with the switch on (cached rollout, k_gru_step, the cached
                                  learner) against off (today's path): a synchronous (train.GraphedIteration) and a pipelined
                                  (train.PipelinedIteration) iteration, timed as `iter`. Whether the switch becomes the default is
-                                 decided from this output (profiles/r09_gru_fused_bench.txt once a run is recorded)."""
+                                 decided from this output (profiles/r09_gru_fused_bench.txt once a run is recorded).
+  learner sync-new | learner sync-base | learner pipe-new | learner pipe-base
+                                 the learner behind that cache: tat-maze-gru --fused-gru at 4096 envs x 20 steps with the embedding
+                                 fold and the grouped weight-gradient launch ON (new) against both OFF (base: fused.fold_embedding
+                                 = fused.use_grouped_dw = False, the learner as it was before the GRU joined them), a synchronous
+                                 and a pipelined iteration, timed as `iter`. `python tools/gru_bench.py --only learner` runs
+                                 these four alone (profiles/r10_gru_learner_bench.txt once a run is recorded)."""
 import os
 import sys
 
@@ -34,7 +40,8 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 VARIANTS = (("bptt", "fused"), ("bptt", "per-step"), ("iter", "tat-maze-gru"), ("iter", "tat-maze-lstm"),
-            ("fused", "sync-on"), ("fused", "sync-off"), ("fused", "pipe-on"), ("fused", "pipe-off"))
+            ("fused", "sync-on"), ("fused", "sync-off"), ("fused", "pipe-on"), ("fused", "pipe-off"),
+            ("learner", "sync-new"), ("learner", "sync-base"), ("learner", "pipe-new"), ("learner", "pipe-base"))
 
 
 def _median_regions(body, regions, sync):
@@ -96,12 +103,15 @@ def one_iter(net, a):
     player.env.close()
 
 
-def one_fused(which, a):
+def one_fused(which, a, kind="fused"):
     import torch
+    from active_tracking_rl_amd import fused
     from active_tracking_rl_amd.train import GraphedIteration, PipelinedIteration, default_args, make_player
     dev = torch.device("cuda:0")
     schedule, switch = which.split("-")
-    args = default_args(num_envs=a.envs, network="tat-maze-gru", fused_gru=switch == "on")
+    if kind == "learner":        # (both module switches are read by every backward pass, the captured ones included: set first)
+        fused.fold_embedding = fused.use_grouped_dw = switch == "new"
+    args = default_args(num_envs=a.envs, network="tat-maze-gru", fused_gru=switch != "off")
     T = args.num_steps
     player, opt = make_player(args, dev)
     sched = GraphedIteration(player, opt, args) if schedule == "sync" else PipelinedIteration(player, opt, args)
@@ -114,7 +124,8 @@ def one_fused(which, a):
     run(a.warmup_steps // T)
     med, lo, hi = _median_regions(lambda: run(a.steps // T), a.regions, lambda: torch.cuda.synchronize(dev))
     agents = [player] if schedule == "sync" else sched.players
-    print(json.dumps(dict(kind="fused", variant=which, envs=a.envs, ms_per_iteration=round(med * 1e3, 5), ms_min=round(lo * 1e3, 5),
+    print(json.dumps(dict(kind=kind, variant=which, envs=a.envs, fold_embedding=bool(fused.fold_embedding),
+                          grouped_dw=bool(fused.use_grouped_dw), ms_per_iteration=round(med * 1e3, 5), ms_min=round(lo * 1e3, 5),
                           ms_max=round(hi * 1e3, 5), regions=a.regions, steps=a.steps, warmup=a.warmup_steps,
                           cached=all(p._cache is not None for p in agents),
                           env_step_fused=bool(player.model.env_step_fused_seen))), flush=True)
@@ -124,6 +135,7 @@ def one_fused(which, a):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--one", nargs=2, metavar=("KIND", "VARIANT"))
+    ap.add_argument("--only", choices=sorted(set(k for k, _ in VARIANTS)), help="the variants of one kind alone")
     ap.add_argument("--envs", type=int, default=4096)
     ap.add_argument("--warmup", type=int, default=20, help="bptt: calls before the timed regions")
     ap.add_argument("--calls", type=int, default=50, help="bptt: calls per region")
@@ -134,10 +146,12 @@ def main():
     a = ap.parse_args()
     assert a.warmup_steps >= 200 and a.steps >= 200 and a.regions >= 5 and a.calls >= 10
     if a.one:
-        dict(bptt=one_bptt, iter=one_iter, fused=one_fused)[a.one[0]](a.one[1], a)
+        dict(bptt=one_bptt, iter=one_iter, fused=one_fused, learner=lambda v, a_: one_fused(v, a_, kind="learner"))[a.one[0]](a.one[1], a)
         return
     rows = []
     for kind, variant in VARIANTS:
+        if a.only and kind != a.only:
+            continue
         cmd = [sys.executable, os.path.abspath(__file__), "--one", kind, variant, "--envs", str(a.envs), "--warmup", str(a.warmup),
                "--calls", str(a.calls), "--warmup-steps", str(a.warmup_steps), "--steps", str(a.steps), "--regions", str(a.regions)]
         r = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT, timeout=a.timeout)
@@ -148,20 +162,28 @@ def main():
         print(json.dumps(rows[-1]), flush=True)
     b = {r["variant"]: r for r in rows if r["kind"] == "bptt"}
     it = {r["variant"]: r for r in rows if r["kind"] == "iter"}
-    print("\nGRU BPTT, %d envs x 20 steps, 2 players (median of %d regions of %d calls): one launch %.1f us, per step %.1f us, "
-          "ratio %.2f" % (a.envs, a.regions, a.calls, b["fused"]["us_per_call"], b["per-step"]["us_per_call"],
-                          b["per-step"]["us_per_call"] / b["fused"]["us_per_call"]))
-    print("synchronous iteration, %d envs (median of %d regions of %d env steps): tat-maze-gru %.4f ms (no rollout cache), "
-          "tat-maze-lstm %.4f ms (cached path), gru / lstm %.2f"
-          % (a.envs, a.regions, a.steps, it["tat-maze-gru"]["ms_per_iteration"], it["tat-maze-lstm"]["ms_per_iteration"],
-             it["tat-maze-gru"]["ms_per_iteration"] / it["tat-maze-lstm"]["ms_per_iteration"]))
+    print()
+    if b:
+        print("GRU BPTT, %d envs x 20 steps, 2 players (median of %d regions of %d calls): one launch %.1f us, per step %.1f us, "
+              "ratio %.2f" % (a.envs, a.regions, a.calls, b["fused"]["us_per_call"], b["per-step"]["us_per_call"],
+                              b["per-step"]["us_per_call"] / b["fused"]["us_per_call"]))
+    if it:
+        print("synchronous iteration, %d envs (median of %d regions of %d env steps): tat-maze-gru %.4f ms (no rollout cache), "
+              "tat-maze-lstm %.4f ms (cached path), gru / lstm %.2f"
+              % (a.envs, a.regions, a.steps, it["tat-maze-gru"]["ms_per_iteration"], it["tat-maze-lstm"]["ms_per_iteration"],
+                 it["tat-maze-gru"]["ms_per_iteration"] / it["tat-maze-lstm"]["ms_per_iteration"]))
     f = {r["variant"]: r for r in rows if r["kind"] == "fused"}
-    for sched, name in (("sync", "synchronous"), ("pipe", "pipelined")):
+    for sched, name in (("sync", "synchronous"), ("pipe", "pipelined")) if f else ():
         on, off = f[sched + "-on"], f[sched + "-off"]
         print("%s iteration of tat-maze-gru, %d envs: --fused-gru %.4f ms (cached %s), without %.4f ms (cached %s), on / off %.3f"
               % (name, a.envs, on["ms_per_iteration"], on["cached"], off["ms_per_iteration"], off["cached"],
                  on["ms_per_iteration"] / off["ms_per_iteration"]))
-
+    ln = {r["variant"]: r for r in rows if r["kind"] == "learner"}
+    for sched, name in (("sync", "synchronous"), ("pipe", "pipelined")) if ln else ():
+        new, base = ln[sched + "-new"], ln[sched + "-base"]
+        print("%s iteration of tat-maze-gru --fused-gru, %d envs: fold + grouped launch %.4f ms, both off %.4f ms, new / base %.3f"
+              % (name, a.envs, new["ms_per_iteration"], base["ms_per_iteration"],
+                 new["ms_per_iteration"] / base["ms_per_iteration"]))
 
 if __name__ == "__main__":
     main()
