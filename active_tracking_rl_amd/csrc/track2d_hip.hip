@@ -26,6 +26,7 @@
 #include "atr_cell.h"
 #include "coop_gemm.h"
 #include "t2d_device.h"
+#include "t2d_trace_view.h"
 
 #ifndef T2D_EXP
 #define T2D_EXP 0
@@ -2386,6 +2387,9 @@ struct t2d_handle {
     void *np_act = nullptr;
     hipStream_t pg_stream = nullptr;
     hipEvent_t ev_pg_fork = nullptr, ev_pg_join = nullptr;
+    // episode-trace store of csrc/render_hip.hip (t2d_trace_attach): owned here, freed by t2d_destroy through trace_free
+    void *trace = nullptr;
+    void (*trace_free)(void *) = nullptr;
 };
 constexpr int kCoopCtlSets = 4, kCoopCtlWords = 8 * 16;
 
@@ -2557,6 +2561,7 @@ extern "C" int t2d_destroy(t2d_handle *h)
         if (p) (void)hipFree(p);
     if (h->coop_ctl) (void)hipFree(h->coop_ctl);
     if (h->np_act) (void)hipFree(h->np_act);
+    if (h->trace && h->trace_free) h->trace_free(h->trace);
     for (void *p : {(void *)s.g_maps, (void *)s.g_ep, (void *)s.pg_stats, (void *)s.np_mt, (void *)s.np_nav})
         if (p) (void)hipFree(p);
     if (h->pg_stream) {
@@ -2565,6 +2570,16 @@ extern "C" int t2d_destroy(t2d_handle *h)
         (void)hipEventDestroy(h->ev_pg_fork); (void)hipEventDestroy(h->ev_pg_join);
     }
     delete h;
+    return T2D_OK;
+}
+
+// The internal accessor of csrc/render_hip.hip (t2d_trace_view.h): the arrays the trace and render kernels read.
+extern "C" int t2d_trace_view_get(t2d_handle *h, t2d_trace_view *out)
+{
+    if (!h || !out) return fail(T2D_ERR_INVALID, "t2d_trace_view_get: null argument");
+    out->device = h->device; out->n = h->s.n; out->auto_reset = h->s.auto_reset;
+    out->maps = h->s.maps; out->pos = h->s.pos; out->cnt = h->s.cnt; out->faults = h->s.faults;
+    out->store = &h->trace; out->store_free = &h->trace_free;
     return T2D_OK;
 }
 

@@ -49,8 +49,16 @@ class VecEnv(object):
     """Batched env: reset() -> obs [N, A, stack, 1, 13, 13] f32 (device);
     step([a_tracker [N], a_target [N]]) -> (obs, rewards [N, A] f32, done [N] uint8, info)."""
 
-    def __init__(self, env_id, num_envs, device="cuda:0", seed=1, stack_frames=1, env_id_base=0, auto_reset=True,
-                 rescale=False, obs_u8=False, async_gen=None, inv=False, **overrides):
+    def __init__(self, env_id, num_envs, device="cuda:0", seed=1, stack_frames=1, env_id_base=0, auto_reset=None,
+                 rescale=False, obs_u8=False, async_gen=None, inv=False, traces=False, **overrides):
+        # traces: keep the per-env position record on the device (include/track2d_trace.h: reset() / step() add one small launch)
+        # so that render() and info['traces'] exist. It needs the gym protocol (auto_reset=False): with the in-launch auto-reset
+        # a terminal step has already replaced the episode's last state.
+        self.traces = bool(traces)
+        if auto_reset is None:
+            auto_reset = not self.traces
+        if self.traces and auto_reset:
+            raise ValueError("traces=True needs auto_reset=False (a finished env's last cell is gone after an in-launch auto-reset)")
         self.env_id = env_id
         self.num_envs = num_envs
         self.stack_frames = int(stack_frames)
@@ -80,6 +88,8 @@ class VecEnv(object):
         self.device = self.core.device
         self._frames = None
         self._seed = seed
+        if self.traces:
+            self.core.trace_attach()
 
     def seed(self, seed=None):
         """Accepted for protocol compatibility. In the reference env.seed() has no effect on trajectories
@@ -116,6 +126,8 @@ class VecEnv(object):
 
     def reset(self):
         obs = self.core.reset()
+        if self.traces:
+            self.core.trace_begin()
         if self.obs_u8:
             obs = obs.to(torch.uint8)        # values 0/1/2/4: exact
         return self._stack(obs, fill=True)
@@ -126,6 +138,8 @@ class VecEnv(object):
         a0 = actions[0]
         a1 = actions[1] if len(actions) > 1 else None
         obs, rew, done = (self.core.step_u8 if self.obs_u8 else self.core.step)(a0, a1, out=out)
+        if self.traces:
+            self.core.trace_append(done)
         return self._stack(obs, done), rew, done, {}
 
     def fused_step_out(self, out):
@@ -141,6 +155,8 @@ class VecEnv(object):
     def after_fused_step(self, env_out):
         """What step() returns, for a step that fused.act_env_step already ran into env_out's buffers."""
         _, obs, rew, done = env_out
+        if self.traces:
+            self.core.trace_append(done)
         return self._stack(obs, done), rew, done, {}
 
     def rollout_buffers(self, num_steps):
@@ -177,8 +193,16 @@ class VecEnv(object):
     def close(self):
         self.core.close()
 
-    def render(self, *a, **k):
-        raise NotImplementedError("matplotlib rendering (track_1v1.py:170-216) is out of scope")
+    def render(self, mode='human', env=0, scale=4, trace=True):
+        """mode='rgb_array': uint8 [82 * scale, 162 * scale, 3] of env `env`, drawn on the device (t2d_render_rgb): what the
+        reference's figure shows (track_1v1.py:170-216) — the map with the agents and the trace, and the tracker's window.
+        Needs traces=True. mode='human' would need a display."""
+        if mode != 'rgb_array':
+            raise NotImplementedError("render(mode=%r) needs a display (the reference's matplotlib figure, track_1v1.py:184-216); "
+                                      "use render(mode='rgb_array') on an env created with traces=True" % (mode,))
+        if not self.traces:
+            raise NotImplementedError("render(mode='rgb_array') needs an env created with traces=True (create_env: args.render)")
+        return self.core.render_rgb([int(env)], scale=scale, trace=trace)[0].cpu().numpy()
 
 
 class NumpyVecEnv(object):
@@ -297,7 +321,7 @@ class Track2DEnv(object):
     argument-less np.random.seed() calls inside generators.py:41,56 are NOT replayed (they make the reference itself
     irreproducible; the golden vectors were captured with them neutralised)."""
 
-    def __init__(self, env_id, device="cuda:0", seed=1, stack_frames=1, rescale=False, rng="philox", inv=False):
+    def __init__(self, env_id, device="cuda:0", seed=1, stack_frames=1, rescale=False, rng="philox", inv=False, traces=False):
         if rng not in ("philox", "numpy"):
             raise ValueError("rng must be 'philox' or 'numpy'")
         self.rng = rng
@@ -310,7 +334,8 @@ class Track2DEnv(object):
             if self._np.scripted:      # the host drives the target; rewards use w_p = 0 either way (track_1v1.py:147-152)
                 over = dict(target_mode_per_env=np.array([registry.TARGET_CODE["Ext"]], np.uint8))
         self.vec = VecEnv(env_id, 1, device=device, seed=seed, stack_frames=stack_frames, auto_reset=False,
-                          rescale=rescale, inv=inv, **over)
+                          rescale=rescale, inv=inv, traces=traces, **over)
+        self.traces = bool(traces)
         self.observation_space, self.action_space = self.vec.observation_space, self.vec.action_space
 
     def seed(self, seed=None):
@@ -326,6 +351,8 @@ class Track2DEnv(object):
         maze, pos, goals = self._np.reset()
         core = self.vec.core
         core.inject(maze, pos, goals)                      # also zeroes the step / far counters (Track1v1Env.reset)
+        if self.traces:
+            core.trace_begin()
         return self.vec._stack(core.observe(), fill=True)[0].cpu().numpy()
 
     def step(self, action):
@@ -338,6 +365,12 @@ class Track2DEnv(object):
         obs, rew, done, _ = self.vec.step(a)
         d2 = int(self.vec.core.get_state()["d2"][0])
         info = {"distance": float(np.sqrt(float(d2)))}           # track_1v1.py:118
+        if self.traces:                                          # track_1v1.py:90-93,120-123
+            tr = self.vec.core.traces(0, 1)
+            n, pos = int(tr["len"][0]), tr["pos"][0].astype(np.int64)
+            info["traces"] = [pos[0, 0].tolist()] + [pos[k, 1].tolist() for k in range(1, n)]
+            cur = pos[n - 1]
+            info["traces_relative"] = [[cur[i] - cur[j] for i in range(2)] for j in range(2)]
         return obs[0].cpu().numpy(), rew[0].double().cpu().numpy(), bool(done[0].item()), info
 
     def close(self):
@@ -345,11 +378,12 @@ class Track2DEnv(object):
         if self._np is not None:
             self._np.close()
 
-    def render(self, *a, **k):
-        return self.vec.render()
+    def render(self, mode='human', scale=4, trace=True):
+        """mode='rgb_array': one uint8 [H, W, 3] frame (VecEnv.render); mode='human' has no display to draw on."""
+        return self.vec.render(mode=mode, env=0, scale=scale, trace=trace)
 
 
-def create_env(env_id, args, num_envs=None, device=None, env_id_base=0, obs_u8=None, rng=None):
+def create_env(env_id, args, num_envs=None, device=None, env_id_base=0, obs_u8=None, rng=None, traces=None):
     """environment.create_env (environment.py:11-32) for the Track2D ids.
 
     args carries the reference's flags (stack_frames, seed, ...) plus optionally `num_envs` and `gpu_ids`.
@@ -375,7 +409,11 @@ def create_env(env_id, args, num_envs=None, device=None, env_id_base=0, obs_u8=N
     if obs_u8 is None:
         obs_u8 = bool(getattr(args, "obs_u8", False))
     rng = rng if rng is not None else getattr(args, "rng", "philox")
+    # --render: the env keeps episode traces (and runs without the in-launch auto-reset); a training env passes traces=False
+    traces = bool(getattr(args, "render", False)) if traces is None else bool(traces)
     if n > 1 and rng in ("numpy", "numpy-device"):      # the reference-exact mode for a batch: env i on np.random.seed(seed + env_id_base + i)
+        if traces:
+            raise NotImplementedError("episode traces / --render are not wired to the batched rng='numpy' envs")
         if stack != 1 or rescale:
             raise NotImplementedError("rng='numpy' with num_envs > 1 returns raw float32 observations (no frame stack / rescale)")
         # rng="numpy-device" / args.np_device: the streams on the device (t2d_np_attach) where the target mode allows it
@@ -383,5 +421,5 @@ def create_env(env_id, args, num_envs=None, device=None, env_id_base=0, obs_u8=N
         return NumpyVecEnv(env_id, [int(seed) + int(env_id_base) + i for i in range(n)], device=device, device_generators=on_dev)
     if n > 1:
         return VecEnv(env_id, n, device=device, seed=seed, stack_frames=stack, env_id_base=env_id_base, rescale=rescale,
-                      obs_u8=obs_u8, inv=inv)
-    return Track2DEnv(env_id, device=device, seed=seed, stack_frames=stack, rescale=rescale, rng=rng, inv=inv)
+                      obs_u8=obs_u8, inv=inv, traces=traces)
+    return Track2DEnv(env_id, device=device, seed=seed, stack_frames=stack, rescale=rescale, rng=rng, inv=inv, traces=traces)

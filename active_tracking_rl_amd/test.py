@@ -19,14 +19,49 @@ import torch
 from .environment import create_env
 from .model import build_model
 from .player_util import Agent
-from .utils import ScalarWriter, check_path, setup_logger
+from .utils import ScalarWriter, check_path, setup_logger, write_png
+
+
+class FrameWriter(object):
+    """--render: the frames of the first `eps` episodes of an evaluation round, drawn on the device in ONE t2d_render_rgb
+    launch per step and written as <dir>/ep{e:03d}/step{t:04d}.png (t = 0: the reset state); an episode stops producing files
+    after its terminal frame. close() adds <dir>/traces.npz: `pos` / `len` of the trace store for all evaluated episodes."""
+
+    def __init__(self, ev, directory, eps, scale, episodes):
+        self.core, self.dir, self.scale, self.episodes = ev.core, directory, int(scale), int(episodes)
+        self.k = max(0, min(int(eps), int(episodes)))
+        self.ids = torch.arange(self.k, dtype=torch.int32, device=ev.device)
+        self.open = np.ones(self.k, bool)
+        for e in range(self.k):
+            check_path(os.path.join(directory, "ep%03d" % e))
+        check_path(directory)
+
+    def frame(self, t, done=None):
+        if self.k == 0 or not self.open.any():
+            return
+        frames = self.core.render_rgb(self.ids, scale=self.scale).cpu().numpy()
+        fin = np.zeros(self.k, bool) if done is None else (done[:self.k].cpu().numpy() != 0)
+        for e in np.nonzero(self.open)[0]:
+            write_png(os.path.join(self.dir, "ep%03d" % e, "step%04d.png" % t), frames[e])
+        self.open &= ~fin
+
+    def close(self):
+        tr = self.core.traces(0, self.episodes)
+        np.savez_compressed(os.path.join(self.dir, "traces.npz"), pos=tr["pos"], len=tr["len"])
 
 
 @torch.no_grad()
-def evaluate(model, env_id, args, device, episodes, seed=None, graphed=False):
+def evaluate(model, env_id, args, device, episodes, seed=None, graphed=False, render_dir=None):
     """Run `episodes` envs of `env_id` in parallel until each has finished ONE episode. Returns per-episode reward
     sums [episodes, 2] and lengths [episodes] (numpy). graphed: the round on the rollout's kernels as replayed hipGraphs
-    (evaluator.GreedyEvaluator) where they apply, else — with one warning line — the eager round below."""
+    (evaluator.GreedyEvaluator) where they apply, else — with one warning line — the eager round below.
+    render_dir: draw the first args.render_eps episodes into it (FrameWriter). The round then runs here, on a shard without the
+    in-launch auto-reset that keeps episode traces; the round ignores an env after its first done either way, so the returned
+    numbers are those of a round without rendering. (A finished env of such a shard is simply stepped on from where it stands —
+    the step kernels treat it like any other env — while its trace stays closed: no masked reset is needed.)"""
+    if graphed and render_dir is not None:
+        logging.getLogger(__name__).warning("--render uses the eager evaluation round: the graphed step restarts episodes in-launch")
+        graphed = False
     if graphed:
         from . import evaluator
         try:
@@ -34,7 +69,7 @@ def evaluate(model, env_id, args, device, episodes, seed=None, graphed=False):
         except evaluator.Unsupported as ex:
             logging.getLogger(__name__).warning("graphed evaluation falls back to the eager round: %s", ex)
     ev = create_env(env_id, args, num_envs=max(2, episodes), device=str(device),
-                    env_id_base=getattr(args, "eval_env_id_base", 1 << 20))
+                    env_id_base=getattr(args, "eval_env_id_base", 1 << 20), traces=render_dir is not None)
     n = ev.num_envs
     was_training = model.training
     model.eval()
@@ -43,13 +78,21 @@ def evaluate(model, env_id, args, device, episodes, seed=None, graphed=False):
     rsum = torch.zeros(n, player.num_agents, device=device)
     length = torch.zeros(n, dtype=torch.int32, device=device)
     alive = torch.ones(n, dtype=torch.bool, device=device)
-    for _ in range(ev.core_max_steps()):
+    frames = None
+    if render_dir is not None:
+        frames = FrameWriter(ev, render_dir, getattr(args, "render_eps", 4), getattr(args, "render_scale", 4), episodes)
+        frames.frame(0)
+    for t in range(ev.core_max_steps()):
         player.action_test()
+        if frames is not None:
+            frames.frame(t + 1, player.done)
         rsum += player.reward * alive.unsqueeze(1)
         length += alive.to(length.dtype)
         alive &= (player.done == 0)
         if not bool(alive.any()):
             break
+    if frames is not None:
+        frames.close()
     ev.close()
     if was_training:
         model.train()
@@ -125,9 +168,10 @@ def test(args, shared_model, train_modes, n_iters, rounds=None, state=None):
     done_rounds = 0
     while rounds is None or done_rounds < rounds:
         t0 = time.time()
-        rsum, length = evaluate(shared_model, env_id, args, device, args.test_eps,
-                                graphed=bool(getattr(args, "graphed_eval", False)))
         n_iter = int(sum(n_iters))
+        render_dir = os.path.join(args.log_dir, 'render', 'iter{0}'.format(n_iter)) if getattr(args, "render", False) else None
+        rsum, length = evaluate(shared_model, env_id, args, device, args.test_eps,
+                                graphed=bool(getattr(args, "graphed_eval", False)), render_dir=render_dir)
         schedule_train_modes(args, train_modes, n_iter, state)                       # test.py:84-92
         # test.py:93-97: one record per evaluation episode at step n_iter. test/fps in the reference is the env steps per
         # second of the evaluator's one env; here the episodes of a round run as one batch, so it is the round's env steps

@@ -57,7 +57,7 @@ def make_player(args, device, rank=0, world_size=1, env=None, model=None, optimi
     torch.manual_seed(args.seed)          # same init on every rank (replicas must start identical)
     if env is None:
         env = create_env(args.env, args, num_envs=args.num_envs, device=str(device),
-                         env_id_base=rank * args.num_envs)
+                         env_id_base=rank * args.num_envs, traces=False)    # (--render draws the evaluation rounds)
     if model is None:
         model = build_model(env.observation_space, env.action_space, args, device).to(device)
     model.train()

@@ -23,6 +23,28 @@ def check_path(path):
     os.makedirs(path, exist_ok=True)
 
 
+def write_png(path, rgb):
+    """Write a uint8 [H, W, 3] array as an 8-bit RGB PNG with the standard library alone (zlib + struct; filter 0 on every
+    row): the frames of --render, without an imaging package."""
+    import struct
+    import zlib
+
+    import numpy as np
+    a = np.ascontiguousarray(rgb)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError("write_png takes a uint8 [H, W, 3] array, got %s %s" % (a.dtype, a.shape))
+    h, w = a.shape[:2]
+    rows = np.zeros((h, 1 + 3 * w), np.uint8)              # each row: the filter byte (0 = None), then its pixels
+    rows[:, 1:] = a.reshape(h, 3 * w)
+
+    def chunk(kind, body):
+        return struct.pack(">I", len(body)) + kind + body + struct.pack(">I", zlib.crc32(kind + body) & 0xFFFFFFFF)
+
+    with open(path, "wb") as f:
+        f.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0))
+                + chunk(b"IDAT", zlib.compress(rows.tobytes(), 6)) + chunk(b"IEND", b""))
+
+
 class ScalarWriter(object):
     """`writer.add_scalar(tag, value, step)` of the reference's tensorboardX.SummaryWriter (train.py:17,98-104; test.py:19,
     94-98). tensorboardX when it is installed (requirements.txt:4 of the reference pins it; this image has no network),

@@ -48,6 +48,16 @@ ABI_SYMBOLS = (
     "t2d_generator_async", "t2d_generator_join", "t2d_generator_cycle", "t2d_pregrow", "t2d_pregrow_stats",
 )
 
+# ... and every symbol include/track2d_trace.h declares, with its ctypes signature (episode traces + device renderer):
+# name -> argument kinds, 'p' pointer / 'i' int; every function returns int
+TRACE_ABI = {
+    "t2d_trace_attach": "pip", "t2d_trace_begin": "ppp", "t2d_trace_append": "ppp", "t2d_trace_get": "piipppp",
+    "t2d_render_cells": "ppiippp", "t2d_render_rgb": "ppiiipip",
+}
+RENDER_TRACE = 1             # T2D_RENDER_TRACE
+FAULT_RENDER_ID = 32         # T2D_FAULT_RENDER_ID
+RENDER_CELLS_H, RENDER_CELLS_W = 82, 162
+
 
 def load_library():
     """dlopen libtrack2d_hip.so and declare the prototypes. Raises if it has not been built."""
@@ -110,6 +120,10 @@ def load_library():
     L.t2d_rollout_random.argtypes = [vp, i32, u64, vp, vp, vp, vp]
     L.t2d_reward_table.restype = i32
     L.t2d_reward_table.argtypes = [vp, vp, i32, C.c_double, vp, vp, vp]
+    for name, kinds in TRACE_ABI.items():
+        fn = getattr(L, name)
+        fn.restype = i32
+        fn.argtypes = [vp if k == "p" else i32 for k in kinds]
     if L.t2d_abi_version() != ABI_VERSION:
         raise T2DError("libtrack2d_hip.so ABI %d != binding ABI %d" % (L.t2d_abi_version(), ABI_VERSION))
     _lib = L
@@ -191,6 +205,8 @@ class VecTrack2D(object):
         _check(self.L.t2d_create(C.byref(cfg), C.byref(h)))
         self.h = h
         self.auto_reset = bool(auto_reset)
+        self.max_episode_steps = int(max_episode_steps)
+        self.trace_capacity = None      # set by trace_attach()
         self.async_gen = False
         if async_gen and auto_reset and min(10, int(max_episode_steps) or 10) >= 2:
             self.generator_async(True)
@@ -314,6 +330,82 @@ class VecTrack2D(object):
         obs = out if out is not None else self._new_obs()
         _check(self.L.t2d_observe(self.h, C.c_void_p(obs.data_ptr()), self._stream()))
         return obs
+
+    # -- episode traces and the device renderer (include/track2d_trace.h) -----------------------------------
+    def trace_attach(self, capacity=None):
+        """Allocate the per-env position record (auto_reset=False handles only): `capacity` steps per episode, default
+        max_episode_steps."""
+        if capacity is None:
+            capacity = self.max_episode_steps
+            if capacity <= 0:
+                raise T2DError("trace_attach: the handle has no time limit, so a capacity must be given")
+        _check(self.L.t2d_trace_attach(self.h, int(capacity), self._stream()))
+        self.trace_capacity = int(capacity)
+
+    def trace_begin(self, mask=None):
+        """After reset() / inject(): restart the record of every env (or of the envs whose mask byte is non-zero)."""
+        mp = None
+        if mask is not None:
+            mask = mask.to(device=self.device, dtype=torch.uint8).contiguous()
+            assert mask.shape == (self.num_envs,)
+            mp = C.c_void_p(mask.data_ptr())
+        _check(self.L.t2d_trace_begin(self.h, mp, self._stream()))
+
+    def trace_append(self, done):
+        """After a step: record both agents' cells of every open env, then close the envs whose `done` byte is set."""
+        assert done.is_cuda and done.dtype == torch.uint8 and done.is_contiguous() and done.numel() == self.num_envs
+        _check(self.L.t2d_trace_append(self.h, C.c_void_p(done.data_ptr()), self._stream()))
+
+    def traces(self, first=0, count=None):
+        """dict(pos int16 [count, capacity + 1, 2, 2], len int32 [count], dropped uint32 [count]); slot 0 holds the spawns,
+        slot k both agents' cells after the k-th step. Synchronises."""
+        if self.trace_capacity is None:
+            raise T2DError("traces: call trace_attach() first")
+        count = self.num_envs - first if count is None else count
+        pos = np.zeros((count, self.trace_capacity + 1, 2, 2), np.int16)
+        ln, dropped = np.zeros(count, np.int32), np.zeros(count, np.uint32)
+        _check(self.L.t2d_trace_get(self.h, int(first), int(count), _np_ptr(pos), _np_ptr(ln), _np_ptr(dropped), self._stream()))
+        return dict(pos=pos, len=ln, dropped=dropped)
+
+    def _env_ids(self, env_ids, who):
+        """int32 device tensor of the ids. Ids given on the host are checked here; ids already on the device are clamped by
+        the kernel, which sets FAULT_RENDER_ID in faults() (the render calls do not synchronise)."""
+        if isinstance(env_ids, torch.Tensor) and env_ids.is_cuda:
+            ids = env_ids.to(dtype=torch.int32).contiguous().reshape(-1)
+        else:
+            host = np.asarray(env_ids.cpu() if isinstance(env_ids, torch.Tensor) else env_ids, np.int64).reshape(-1)
+            if host.size and (host.min() < 0 or host.max() >= self.num_envs):
+                raise T2DError("%s: env id %d outside [0, %d)" % (who, int(host[(host < 0) | (host >= self.num_envs)][0]), self.num_envs))
+            ids = torch.as_tensor(host.astype(np.int32), device=self.device)
+        return ids
+
+    def render_cells(self, env_ids, trace=True, out=None):
+        """(cells u8 [count, 82, 82], partial u8 [count, 13, 13]) of the listed envs: what the reference's render() draws —
+        the full observation with (trace=True) the trace painted 6 after the agents, 255 outside the env's own side; and the
+        tracker's window."""
+        ids = self._env_ids(env_ids, "render_cells")
+        if out is None:
+            out = (torch.empty((ids.numel(), 82, 82), dtype=torch.uint8, device=self.device),
+                   torch.empty((ids.numel(), 13, 13), dtype=torch.uint8, device=self.device))
+        cells, partial = out
+        _check(self.L.t2d_render_cells(self.h, C.c_void_p(ids.data_ptr()), ids.numel(), RENDER_TRACE if trace else 0,
+                                       C.c_void_p(cells.data_ptr()), C.c_void_p(partial.data_ptr()), self._stream()))
+        return cells, partial
+
+    def render_rgb(self, env_ids, scale=4, trace=True, pitch=None, out=None):
+        """u8 [count, 82 * scale, 162 * scale, 3]: one frame per listed env (map panel, gap, the tracker's window at six times
+        the size), a view of the pitched canvas `out` (u8 [count, 82 * scale, pitch]) without its row padding."""
+        ids = self._env_ids(env_ids, "render_rgb")
+        scale = int(scale)
+        row = 3 * RENDER_CELLS_W * scale
+        if pitch is None:
+            pitch = (row + 15) // 16 * 16
+        if out is None:
+            out = torch.empty((ids.numel(), RENDER_CELLS_H * max(scale, 0), int(pitch)), dtype=torch.uint8, device=self.device)
+        assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == ids.numel() * RENDER_CELLS_H * scale * int(pitch)
+        _check(self.L.t2d_render_rgb(self.h, C.c_void_p(ids.data_ptr()), ids.numel(), scale, RENDER_TRACE if trace else 0,
+                                     C.c_void_p(out.data_ptr()), int(pitch), self._stream()))
+        return out[:, :, :row].unflatten(2, (RENDER_CELLS_W * scale, 3))
 
     # -- parity / test hooks -------------------------------------------------------------------------
     def inject(self, mazes, pos, goals=None, first=0):

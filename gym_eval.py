@@ -27,7 +27,13 @@ parser.add_argument('--load-tracker', default=None, metavar='LCD', help='tracker
 parser.add_argument('--load-target', default=None, metavar='LCD', help='target checkpoint')
 parser.add_argument('--log-dir', default='logs/', metavar='LG', help='folder to save logs')
 parser.add_argument('--csv', default=None, metavar='SV', help='write to csv')
-parser.add_argument('--render', dest='render', action='store_true', help='(not supported on the batched path)')
+parser.add_argument('--render', dest='render', action='store_true',
+                    help='draw the first --render-eps episodes on the device and write them as PNG frames under --render-dir '
+                         '(runs the eager round on a shard that keeps episode traces)')
+parser.add_argument('--render-dir', default=None, metavar='DIR',
+                    help='--render: folder for ep{e:03d}/step{t:04d}.png and traces.npz (default: <log-dir>/render)')
+parser.add_argument('--render-eps', type=int, default=4, metavar='K', help='--render: episodes to draw (default: 4)')
+parser.add_argument('--render-scale', type=int, default=4, metavar='S', help='--render: pixels per map cell, 1..8 (default: 4)')
 parser.add_argument('--network', default='tat-maze-lstm', metavar='M', help='Model type to use')
 parser.add_argument('--stack-frames', type=int, default=1, metavar='SF', help='Choose whether to stack observations')
 parser.add_argument('--seed', type=int, default=1, metavar='S', help='random seed (default: 1)')
@@ -70,7 +76,8 @@ if __name__ == '__main__':
     if args.load_target is not None:
         model.player1.load_state_dict(load(args.load_target))             # :88-92
     args.gpu_ids = [device.index]
-    rsum, length = evaluate(model, args.env, args, device, args.num_episodes, graphed=args.graphed_eval)
+    render_dir = (args.render_dir or os.path.join(args.log_dir, 'render')) if args.render else None
+    rsum, length = evaluate(model, args.env, args, device, args.num_episodes, graphed=args.graphed_eval, render_dir=render_dir)
     reward_mean, reward_std = rsum.mean(0), rsum.std(0)
     len_mean, len_std = length.mean(), length.std()
     success_rate = float((length >= 500).mean())

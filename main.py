@@ -80,7 +80,11 @@ parser.add_argument('--gray', dest='gray', action='store_true', help='gray image
 parser.add_argument('--crop', dest='crop', action='store_true', help='crop image')
 parser.add_argument('--inv', dest='inv', action='store_true', help='inverse image')
 parser.add_argument('--rescale', dest='rescale', action='store_true', help='rescale image to [-1, 1]')
-parser.add_argument('--render', dest='render', action='store_true', help='(not supported on the batched path)')
+parser.add_argument('--render', dest='render', action='store_true',
+                    help='draw the first --render-eps episodes of every test round on the device and write them as PNG frames '
+                         'under <log-dir>/render/iter{n}/ (such rounds run eagerly on a shard that keeps episode traces)')
+parser.add_argument('--render-eps', type=int, default=4, metavar='K', help='--render: episodes to draw per test round (default: 4)')
+parser.add_argument('--render-scale', type=int, default=4, metavar='S', help='--render: pixels per map cell, 1..8 (default: 4)')
 parser.add_argument('--shared-optimizer', dest='shared_optimizer', action='store_true',
                     help='SharedAdam / SharedRMSprop numerics; without it torch.optim.Adam / RMSprop numerics (train.py:45-49)')
 parser.add_argument('--split', dest='split', action='store_true', help='split model to save')
