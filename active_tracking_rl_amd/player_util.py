@@ -287,6 +287,9 @@ class Agent(object):
         stats = getattr(self.env, "episode_stats", None)      # (episode_stats.EpisodeStats: the episodes in flight are gone)
         if stats is not None:
             stats.reset_running()
+        track = getattr(self.env, "tracking_stats", None)     # (tracking_stats.TrackingStats: the next action pairs with no state)
+        if track is not None:
+            track.reset_running()
 
     def clear_actions(self):
         self.values, self.log_probs, self.rewards, self.entropies, self.preds, self.dones = [], [], [], [], [], []

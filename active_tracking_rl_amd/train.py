@@ -97,6 +97,17 @@ def rollout(player, num_steps, fast=True):
             stats.update(buf[1], buf[2])
         else:
             stats.update(torch.stack(player.rewards[-num_steps:]), torch.stack(player.dones[-num_steps:]))
+    # tracking statistics (tracking_stats.TrackingStats, opt-in, attached to the env shard in the same way): one launch over the
+    # windows, rewards, done flags and actions of the rollout store, on the rollout's stream and inside its captured graph. The
+    # actions are the sampler's [T, 2, N] store where there is one (read through its strides as [T, N, 2]), else the stacked list.
+    track = getattr(player.env, "tracking_stats", None)
+    if track is not None:
+        buf = player._buf if fast else None
+        if buf is None or buf[2].shape[0] != num_steps:
+            raise RuntimeError("tracking statistics read the rollout store, and this rollout has none (fast=%s)" % fast)
+        acts = getattr(player, "_actions_buf", None)
+        acts = acts.permute(0, 2, 1) if acts is not None else torch.stack(player.actions[-num_steps:])
+        track.update(buf[0], buf[1], buf[2], acts)
     # A rollout that is not a whole number of generator stamp cycles restarts the stamps (so that a captured rollout
     # replays consistently); otherwise forked generator launches stay in flight under the learner's kernels.
     if hasattr(player.env, "flush") and num_steps % getattr(player.env, "generator_cycle", 1) != 0:
@@ -800,6 +811,10 @@ def train(rank, args, shared_model, optimizer, train_modes, n_iters, env=None):
     if getattr(args, "episode_stats", False):       # (make_player has just reset the shard: every env is at step 0)
         from .episode_stats import EpisodeStats
         ep_stats = EpisodeStats(player.env, device)
+    track = None
+    if getattr(args, "tracking_stats", False):
+        from .tracking_stats import TrackingStats
+        track = TrackingStats(player.env, device)
     n_iter = 0
     try:
         while True:
@@ -817,6 +832,8 @@ def train(rank, args, shared_model, optimizer, train_modes, n_iters, env=None):
                                   player.num_agents)
                 if ep_stats is not None:
                     ep_stats.record(writer, player.n_steps, rank)
+                if track is not None:
+                    track.record(writer, player.n_steps, rank, args.log_dir)
                 writer.flush()
             if train_modes[rank] == -100 or n_iter * world > args.max_step:   # test.py:129-134 stop rule
                 break

@@ -112,6 +112,11 @@ parser.add_argument('--episode-stats', dest='episode_stats', action='store_true'
                     help='keep returns and lengths of the training episodes on the device (one more launch per rollout) and '
                          'write train/reward_0, train/reward_1, train/eps_len, train/success_rate, train/episodes with every '
                          '--log-every record')
+parser.add_argument('--tracking-stats', dest='tracking_stats', action='store_true',
+                    help='count on the device where the target sits in the tracker\'s window and which actions both players take '
+                         'from there (one more launch per rollout); every --log-every record writes train/in_view_rate, '
+                         'train/in_range_rate, train/colocated_rate, train/mean_distance, train/tracker_toward_rate, '
+                         'train/target_away_rate and heatmaps/target_offset_<steps>.png + .npz under --log-dir')
 parser.add_argument('--adv-step', type=int, default=None, metavar='AS',
                     help="--train-mode 2 only: iterations the TARGET trains before the evaluator hands back to the tracker "
                          "(test.py:88-91 of the reference reads args.adv_step, which its own main.py never defines)")
@@ -152,6 +157,10 @@ if __name__ == '__main__':
     if args.episode_stats:      # attached to the fresh shard, before any schedule captures a rollout over it
         from active_tracking_rl_amd.episode_stats import EpisodeStats
         ep_stats = EpisodeStats(player.env, device)
+    track_stats = None
+    if args.tracking_stats:
+        from active_tracking_rl_amd.tracking_stats import TrackingStats
+        track_stats = TrackingStats(player.env, device)
     if args.load_model_dir is not None:
         saved_state = torch.load(args.load_model_dir, map_location=lambda storage, loc: storage)
         player.model.load_state_dict(saved_state)
@@ -181,12 +190,16 @@ if __name__ == '__main__':
     elif args.burn_in > 0 and rank == 0:
         print("warning: --burn-in %d ignored with --no-graph (the eager loop has no rollback of its updates)" % args.burn_in,
               file=sys.stderr, flush=True)
-    if ep_stats is not None and sched is not None:
+    if (ep_stats is not None or track_stats is not None) and sched is not None:
         # warm-up iterations, tune_streams trials and burn-in moved the shard on without being training: the episodes they
-        # finished are drained and dropped; the episodes in flight carry on and are counted whole when they end
+        # finished (the samples they counted) are drained and dropped; the episodes in flight carry on and are counted whole
+        # when they end
         sched.finish()
         torch.cuda.synchronize(device)
-        ep_stats.drain()
+        if ep_stats is not None:
+            ep_stats.drain()
+        if track_stats is not None:
+            track_stats.drain()
     step = sched.run if sched is not None else None
     drain = getattr(sched, "finish", lambda: None)          # pipelined: both streams joined before the host reads anything
     it = 0
@@ -219,6 +232,8 @@ if __name__ == '__main__':
             log_train_scalars(writer, stats, train_modes[rank], fps, it * args.num_steps * player.num_envs, player.num_agents)
             if ep_stats is not None:    # drain, pool over ranks, summarise: episodes finished since the last record
                 ep_stats.record(writer, it * args.num_steps * player.num_envs, rank)
+            if track_stats is not None:
+                track_stats.record(writer, it * args.num_steps * player.num_envs, rank, args.log_dir)
             writer.flush()
             t_log, it_log = time.time(), it
         if it % args.test_every == 0 or it > args.max_step:

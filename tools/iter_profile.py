@@ -1,7 +1,8 @@
 """Per-iteration kernel table of an A3C iteration (hipGraph replay): run under rocprofv3 --kernel-trace --stats, then
 tools/summarize_prof.py; `calls / ITERS` and `total / ITERS` are per iteration (plus two eager warm-up iterations).
   python tools/iter_profile.py [ITERS] [env] [num_envs] [network] [aux] [train_mode]      (default: the headline config)
-ITER_PROFILE_SCHEDULE=pipelined profiles the two-stream schedule instead (kernel durations BESIDE the other chain)."""
+ITER_PROFILE_SCHEDULE=pipelined profiles the two-stream schedule instead (kernel durations BESIDE the other chain).
+ITER_PROFILE_TRACKING_STATS=1 attaches tracking_stats.TrackingStats to the shard (k_track_stats: one launch per rollout)."""
 import os
 import sys
 import torch
@@ -13,6 +14,9 @@ if len(sys.argv) > 2:
 dev = torch.device("cuda:0")
 args = default_args(**over)
 player, opt = make_player(args, dev)
+if os.environ.get("ITER_PROFILE_TRACKING_STATS") == "1":
+    from active_tracking_rl_amd.tracking_stats import TrackingStats
+    TrackingStats(player.env, dev)
 if os.environ.get("ITER_PROFILE_SCHEDULE") == "pipelined":
     it = PipelinedIteration(player, opt, args)
     it.tune_streams()
