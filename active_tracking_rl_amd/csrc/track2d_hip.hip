@@ -26,6 +26,7 @@
 #include "atr_cell.h"
 #include "coop_gemm.h"
 #include "t2d_device.h"
+#include "t2d_state_view.h"
 #include "t2d_trace_view.h"
 
 #ifndef T2D_EXP
@@ -2580,6 +2581,27 @@ extern "C" int t2d_trace_view_get(t2d_handle *h, t2d_trace_view *out)
     out->device = h->device; out->n = h->s.n; out->auto_reset = h->s.auto_reset;
     out->maps = h->s.maps; out->pos = h->s.pos; out->cnt = h->s.cnt; out->faults = h->s.faults;
     out->store = &h->trace; out->store_free = &h->trace_free;
+    return T2D_OK;
+}
+
+// The internal accessor of csrc/state_hip.hip (t2d_state_view.h): the state arrays in the snapshot blob's payload order.
+extern "C" int t2d_state_view_get(t2d_handle *h, t2d_state_view *out)
+{
+    if (!h || !out) return fail(T2D_ERR_INVALID, "t2d_state_view_get: null argument");
+    const DevState &s = h->s;
+    out->device = h->device; out->n = s.n; out->auto_reset = s.auto_reset; out->max_steps = s.max_steps;
+    out->obs_full = s.obs_full; out->amask = s.amask;
+    out->env_base = s.env_base; out->k0 = s.k0; out->k1 = s.k1;
+    out->ready = h->reset_done && (h->primed || !s.auto_reset) ? 1 : 0;
+    out->np_attached = s.np_mt != nullptr ? 1 : 0;
+    out->trace_attached = h->trace != nullptr ? 1 : 0;
+    out->cfg = s.cfg; out->random_step = &h->random_step;
+    uint32_t *const arrs[kStateArrays] = {
+        s.maps, s.pos, s.goals, s.cnt, s.episode, s.plan, s.tctr, s.navgoal, s.nav2, s.d2,
+        s.n_maps, s.n_pos, s.n_goals, s.n_plan, s.n_tctr, s.n_navgoal, s.n_nav2, s.n_d2, s.n_win,
+        s.dirf, s.n_dirf, s.p_field, s.p_goal, s.p_tctr, s.p_state,
+        s.g_maps, s.g_ep};
+    for (int i = 0; i < kStateArrays; i++) out->arr[i] = arrs[i];
     return T2D_OK;
 }
 

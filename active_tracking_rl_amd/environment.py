@@ -67,6 +67,7 @@ class VecEnv(object):
         # is -ob, its step observations are mx_d - ob = 255 - ob (of the RESCALED image — the reference's own arithmetic, kept)
         self.inv = bool(inv) and self.rescale
         self._inv_flags = None
+        self._inv_fresh = None          # which envs' last observation was the first of its episode (observe() repeats its sign)
         # t2d_generator_async (map generation forked onto the library's stream, under the following steps) is opt-in:
         # inside a captured hipGraph every fork/join of a side branch costs ~200 us on this ROCm (measured,
         # profiles/r02_async_generator_ab.txt), more than the generator launch it hides
@@ -96,24 +97,29 @@ class VecEnv(object):
         (track_1v1.py:129-132 sets an RNG that is never read); here the Philox key is fixed at construction."""
         return [seed]
 
-    def _stack(self, obs, done=None, fill=False):
-        # obs [N, A, 13, 13] -> [N, A, stack, 1, 13, 13]
+    def _stack(self, obs, done=None, fill=False, peek=False):
+        # obs [N, A, 13, 13] -> [N, A, stack, 1, 13, 13]; peek (observe()): no coin flip is drawn and the stack does not advance
         if self.rescale:   # Rescale.rescale, same float32 operation order: ((clip(x) - 0) * 2) / 255 + (-1)
             obs = obs.clamp(0.0, 255.0).mul(2.0).div(255.0).add(-1.0)
             if self.inv:
                 n = obs.shape[0]
-                if fill or self._inv_flags is None:      # reset(): every env draws its flag and returns -ob
+                if peek and self._inv_flags is not None:
+                    fresh = self._inv_fresh
+                elif fill or self._inv_flags is None:    # reset(): every env draws its flag and returns -ob
                     self._inv_flags = torch.rand(n, device=obs.device) < 0.5
                     fresh = torch.ones(n, dtype=torch.bool, device=obs.device)
                 else:                                    # step(): auto-reset envs start a new episode (new flag, -ob)
                     fresh = done.bool() if done is not None else torch.zeros(n, dtype=torch.bool, device=obs.device)
                     self._inv_flags = torch.where(fresh, torch.rand(n, device=obs.device) < 0.5, self._inv_flags)
+                self._inv_fresh = fresh
                 shp = (n,) + (1,) * (obs.dim() - 1)
                 f, r = self._inv_flags.view(shp), fresh.view(shp)
                 obs = torch.where(f & r, -obs, torch.where(f & ~r, 255.0 - obs, obs))
         cur = obs.unsqueeze(2).unsqueeze(3)
         if self.stack_frames == 1:
             return cur
+        if peek and self._frames is not None:
+            return self._frames
         if fill or self._frames is None:
             self._frames = cur.expand(-1, -1, self.stack_frames, -1, -1, -1).clone()
         else:
@@ -141,6 +147,50 @@ class VecEnv(object):
         if self.traces:
             self.core.trace_append(done)
         return self._stack(obs, done), rew, done, {}
+
+    def observe(self):
+        """The current observation in reset()'s shape, without stepping (t2d_observe): the frame stack as it stands, the
+        running episodes' --inv flags."""
+        obs = self.core.observe()
+        if self.obs_u8:
+            obs = obs.to(torch.uint8)
+        return self._stack(obs, peek=True)
+
+    # -- snapshots (include/track2d_state.h) ------------------------------------------------------------------
+    def _env_mask(self, mask):
+        return None if mask is None else torch.as_tensor(mask).to(device=self.device).reshape(self.num_envs) != 0
+
+    def clone_state(self, mask=None):
+        """The state of this shard as a dict: the core's EnvSnapshot (device-resident; it always holds every env) with the
+        frame stack and the --inv flags beside it. `mask` ([N], non-zero = take part) is remembered as the default of
+        restore_state."""
+        if self.traces:
+            raise NotImplementedError("clone_state: an env created with traces=True keeps an episode record that is not part "
+                                      "of a snapshot")
+        snap = self.core.snapshot().save()
+        keep = lambda t: None if t is None else t.clone()
+        return dict(core=snap, frames=keep(self._frames), inv_flags=keep(self._inv_flags), inv_fresh=keep(self._inv_fresh),
+                    mask=self._env_mask(mask))
+
+    def restore_state(self, state, mask=None):
+        """Put the envs of `mask` (default: the mask clone_state was given, else all) back to `state`, a clone_state() of this
+        env: under the same actions (and the same --inv coin flips) they repeat what followed the clone, bit for bit."""
+        if self.traces:
+            raise NotImplementedError("restore_state: an env created with traces=True keeps an episode record that is not part "
+                                      "of a snapshot")
+        if state["core"].env is not self.core:
+            raise ValueError("restore_state: the state was cloned from another env (EnvSnapshot.to_bytes / load_bytes carry a "
+                             "snapshot between envs of one configuration)")
+        m = self._env_mask(mask) if mask is not None else state["mask"]
+        state["core"].restore(m)
+        for name in ("_frames", "_inv_flags", "_inv_fresh"):
+            saved, cur = state[name[1:]], getattr(self, name)
+            if saved is None:
+                continue
+            if m is None or cur is None:
+                setattr(self, name, saved.clone())
+            else:
+                setattr(self, name, torch.where(m.view((-1,) + (1,) * (saved.dim() - 1)), saved, cur))
 
     def fused_step_out(self, out):
         """(core, obs, rew, done) for fused.act_env_step — the env step inside the policy step's last launch — when this
@@ -372,6 +422,22 @@ class Track2DEnv(object):
             cur = pos[n - 1]
             info["traces_relative"] = [[cur[i] - cur[j] for i in range(2)] for j in range(2)]
         return obs[0].cpu().numpy(), rew[0].double().cpu().numpy(), bool(done[0].item()), info
+
+    def clone_state(self):
+        """VecEnv.clone_state of the one env (what copy.deepcopy(env) gives the reference's user)."""
+        self._no_snapshot("clone_state")
+        return self.vec.clone_state()
+
+    def restore_state(self, state):
+        self._no_snapshot("restore_state")
+        self.vec.restore_state(state)
+
+    def _no_snapshot(self, who):
+        if self.traces:
+            raise NotImplementedError("%s: an env created with traces=True keeps an episode record that is not part of a "
+                                      "snapshot" % who)
+        if self._np is not None:
+            raise NotImplementedError("%s: rng='numpy' keeps the episode stream on the host, which a snapshot does not hold" % who)
 
     def close(self):
         self.vec.close()

@@ -20,6 +20,17 @@ import torch
 import torch.distributed as dist
 
 
+SHARD_META_FIELDS = ("env", "N", "env_id_base", "network", "rnn_out")
+
+
+def shard_meta_mismatch(saved, mine):
+    """The first field of SHARD_META_FIELDS in which two shard `meta` dicts differ (a missing field differs), or None."""
+    for key in SHARD_META_FIELDS:
+        if key not in saved or key not in mine or saved[key] != mine[key]:
+            return key
+    return None
+
+
 class Agent(object):
     def __init__(self, model, env, args, state, device):
         self.model = model
@@ -290,6 +301,61 @@ class Agent(object):
         track = getattr(self.env, "tracking_stats", None)     # (tracking_stats.TrackingStats: the next action pairs with no state)
         if track is not None:
             track.reset_running()
+
+    # -- the shard as a file (main.py --save-shard-state / --load-shard-state) ---------------------------------------
+    def _shard_meta(self):
+        core = self.env.core
+        return dict(env=self.env.env_id, N=int(self.num_envs), env_id_base=int(core.env_id_base),
+                    network=str(self.args.network), rnn_out=int(self.rnn_out))
+
+    def shard_state(self, carry=None):
+        """The env shard and the players' recurrent rows as a dict of CPU tensors (torch.save-able): the env snapshot blob
+        (include/track2d_state.h) as uint8, hxs, cxs, eps_len, done, the action sampler's counter and seed where the model has
+        one, the env's frame stack and --inv flags where it keeps them, and `meta`. carry: a graphed schedule's carry dict, read
+        in place of this player's own tensors. Call between rollouts, with the device idle (it synchronises)."""
+        src = carry if carry is not None else dict(hxs=self.hxs, cxs=self.cxs, eps_len=self.eps_len, done=self.done)
+        if getattr(self, "_shard_snap", None) is None:
+            self._shard_snap = self.env.core.snapshot()
+        blob = self._shard_snap.save().to_bytes()
+        d = dict(meta=self._shard_meta(), env=torch.frombuffer(bytearray(blob), dtype=torch.uint8))
+        for key in ("hxs", "cxs", "eps_len", "done"):
+            d[key] = src[key].detach().cpu().clone()
+        sampler = getattr(self.model, "_sampler", None)
+        if sampler is not None:
+            d["sampler_counter"], d["sampler_seed"] = sampler.counter.cpu().clone(), int(sampler.seed)
+        for key in ("_frames", "_inv_flags", "_inv_fresh"):
+            t = getattr(self.env, key, None)
+            if t is not None:
+                d["env" + key] = t.cpu().clone()
+        return d
+
+    def load_shard_state(self, d):
+        """Continue the shard of a shard_state() dict: env state, recurrent rows, episode lengths, done flags and the sampler's
+        stream; self.state becomes the restored envs' current observation. ValueError names the first `meta` field that differs
+        (the env library refuses a blob of another seed / time limit / per-env configuration with its own text)."""
+        key = shard_meta_mismatch(d["meta"], self._shard_meta())
+        if key is not None:
+            raise ValueError("load_shard_state: the saved shard's %s is %r, this player's is %r"
+                             % (key, d["meta"].get(key), self._shard_meta().get(key)))
+        for key in ("hxs", "cxs"):
+            if tuple(d[key].shape) != tuple(getattr(self, key).shape):
+                raise ValueError("load_shard_state: %s has shape %s, this player's %s"
+                                 % (key, tuple(d[key].shape), tuple(getattr(self, key).shape)))
+        if getattr(self, "_shard_snap", None) is None:
+            self._shard_snap = self.env.core.snapshot()
+        self._shard_snap.load_bytes(d["env"].numpy()).restore()
+        self.hxs, self.cxs = d["hxs"].to(self.device), d["cxs"].to(self.device)
+        self.eps_len, self.done = d["eps_len"].to(self.device), d["done"].to(self.device)
+        if "sampler_counter" in d:
+            from . import fused
+            if getattr(self.model, "_sampler", None) is None:
+                self.model._sampler = fused.ActionSampler(self.device, seed=d["sampler_seed"])
+            self.model._sampler.seed = int(d["sampler_seed"])
+            self.model._sampler.counter.copy_(d["sampler_counter"])
+        for key in ("_frames", "_inv_flags", "_inv_fresh"):
+            if "env" + key in d:
+                setattr(self.env, key, d["env" + key].to(self.device))
+        self.state = self.env.observe()
 
     def clear_actions(self):
         self.values, self.log_probs, self.rewards, self.entropies, self.preds, self.dones = [], [], [], [], [], []

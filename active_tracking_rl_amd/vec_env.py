@@ -10,6 +10,7 @@ gym's TimeLimit(500) (gym_track2d/__init__.py:17) and frame_stack's float32 cast
 """
 import ctypes as C
 import os
+import struct
 
 import numpy as np
 import torch
@@ -139,6 +140,133 @@ def _np_ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+# ... and include/track2d_state.h (env shard snapshots): name -> (restype, [argtypes]); tests/test_env_snapshot_cpu.py holds the
+# table to the header. Every int result is a status; t2d_snapshot_bytes returns a size.
+STATE_PROTOTYPES = {
+    "t2d_snapshot_create": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "t2d_snapshot_destroy": (C.c_int, [C.c_void_p]),
+    "t2d_snapshot_save": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "t2d_snapshot_restore": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "t2d_snapshot_bytes": (C.c_longlong, [C.c_void_p]),
+    "t2d_snapshot_export": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "t2d_snapshot_import": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
+}
+_state_lib = None
+
+
+def _state_errcheck(name):
+    """The ctypes errcheck of a status-returning snapshot entry point: a non-zero status raises T2DError naming the entry
+    point, with the library's own text."""
+    def check(status, func=None, args=None):
+        if status != 0:
+            raise T2DError("%s failed (%d): %s" % (name, status, load_library().t2d_last_error().decode()))
+        return status
+    return check
+
+
+def state_lib():
+    """The library with include/track2d_state.h's prototypes declared (a library without them is an error)."""
+    global _state_lib
+    if _state_lib is None:
+        L = load_library()
+        for name, (restype, argtypes) in STATE_PROTOTYPES.items():
+            f = getattr(L, name)
+            f.restype, f.argtypes = restype, argtypes
+            if restype is C.c_int:
+                f.errcheck = _state_errcheck(name)
+        _state_lib = L
+    return _state_lib
+
+
+SNAPSHOT_MAGIC = b"T2DSNAP\0"
+SNAPSHOT_VERSION = 1
+SNAPSHOT_HEADER_BYTES = 96
+_SNAPSHOT_HEADER = struct.Struct("<8sIIIIQiiIIQIIQ24x")      # the blob header of include/track2d_state.h, little-endian
+_SNAPSHOT_FIELDS = ("magic", "version", "header_bytes", "num_envs", "env_id_base", "seed", "max_episode_steps", "auto_reset",
+                    "obs_type", "action_type", "cfg_hash", "sections", "random_step", "payload_bytes")
+assert _SNAPSHOT_HEADER.size == SNAPSHOT_HEADER_BYTES
+
+
+def snapshot_header(b):
+    """The header of a snapshot blob (EnvSnapshot.to_bytes, t2d_snapshot_export) as a dict, parsed without the library.
+    ValueError for a truncated header, a wrong magic or version, or a size field the blob cannot hold."""
+    b = memoryview(b).cast("B")          # bytes, bytearray, a numpy uint8 array
+    total = b.nbytes
+    if total < SNAPSHOT_HEADER_BYTES:
+        raise ValueError("snapshot blob: %d bytes, shorter than the %d-byte header" % (total, SNAPSHOT_HEADER_BYTES))
+    h = dict(zip(_SNAPSHOT_FIELDS, _SNAPSHOT_HEADER.unpack_from(b, 0)))
+    if h["magic"] != SNAPSHOT_MAGIC:
+        raise ValueError("snapshot blob: wrong magic %r" % (h["magic"],))
+    if h["version"] != SNAPSHOT_VERSION:
+        raise ValueError("snapshot blob: format version %d, this reader knows %d" % (h["version"], SNAPSHOT_VERSION))
+    if h["header_bytes"] != SNAPSHOT_HEADER_BYTES:
+        raise ValueError("snapshot blob: header size %d, expected %d" % (h["header_bytes"], SNAPSHOT_HEADER_BYTES))
+    if h["header_bytes"] + h["payload_bytes"] > total:
+        raise ValueError("snapshot blob: header + payload = %d bytes, the blob has %d"
+                         % (h["header_bytes"] + h["payload_bytes"], total))
+    del h["magic"]
+    return h
+
+
+class EnvSnapshot(object):
+    """A device-resident copy of the state of every env of one VecTrack2D (t2d_snapshot, include/track2d_state.h). Made by
+    VecTrack2D.snapshot(); holds a reference to its env and is freed by close() or with the object."""
+
+    def __init__(self, env):
+        self.L = state_lib()
+        self.env = env
+        s = C.c_void_p()
+        self.L.t2d_snapshot_create(env.h, C.byref(s))
+        self.s = s
+
+    def close(self):
+        if getattr(self, "s", None):
+            self.L.t2d_snapshot_destroy(self.s)
+            self.s = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _mask(self, mask):
+        if mask is None:
+            return None, None
+        mask = torch.as_tensor(mask).to(device=self.env.device, dtype=torch.uint8).contiguous()
+        assert mask.shape == (self.env.num_envs,)
+        return mask, C.c_void_p(mask.data_ptr())
+
+    def save(self, mask=None):
+        """env -> snapshot for every env, or for those whose mask byte is non-zero (the first save must cover every env)."""
+        keep, mp = self._mask(mask)
+        self.L.t2d_snapshot_save(self.env.h, self.s, mp, self.env._stream())
+        return self
+
+    def restore(self, mask=None):
+        """snapshot -> env for every env, or for those whose mask byte is non-zero."""
+        keep, mp = self._mask(mask)
+        self.L.t2d_snapshot_restore(self.env.h, self.s, mp, self.env._stream())
+        return self
+
+    @property
+    def nbytes(self):
+        return int(self.L.t2d_snapshot_bytes(self.s))
+
+    def to_bytes(self):
+        """The snapshot as one host blob (header + arrays, include/track2d_state.h). Synchronises."""
+        buf = np.empty(self.nbytes, np.uint8)
+        self.L.t2d_snapshot_export(self.s, _np_ptr(buf), buf.size, self.env._stream())
+        return buf.tobytes()
+
+    def load_bytes(self, b):
+        """Fill the snapshot from a blob of an env with the same configuration (T2DError names the first field that differs).
+        Synchronises."""
+        buf = np.frombuffer(b, np.uint8) if not isinstance(b, np.ndarray) else np.ascontiguousarray(b, np.uint8)
+        self.L.t2d_snapshot_import(self.s, _np_ptr(buf), buf.size, self.env._stream())
+        return self
+
+
 class VecTrack2D(object):
     """N independent Track2D envs stepped by one kernel launch.
 
@@ -166,6 +294,7 @@ class VecTrack2D(object):
         self.env_id = env_id
         self.device = torch.device(device)
         self.num_envs = int(num_envs)
+        self.env_id_base = int(env_id_base)
         self.map_type, self.target_mode, self.level = map_type, target_mode, int(level)
         cfg = _Config()
         cfg.abi_version = ABI_VERSION
@@ -330,6 +459,10 @@ class VecTrack2D(object):
         obs = out if out is not None else self._new_obs()
         _check(self.L.t2d_observe(self.h, C.c_void_p(obs.data_ptr()), self._stream()))
         return obs
+
+    def snapshot(self):
+        """A new EnvSnapshot of this env (contents undefined until its first save() or load_bytes())."""
+        return EnvSnapshot(self)
 
     # -- episode traces and the device renderer (include/track2d_trace.h) -----------------------------------
     def trace_attach(self, capacity=None):

@@ -117,6 +117,13 @@ parser.add_argument('--tracking-stats', dest='tracking_stats', action='store_tru
                          'from there (one more launch per rollout); every --log-every record writes train/in_view_rate, '
                          'train/in_range_rate, train/colocated_rate, train/mean_distance, train/tracker_toward_rate, '
                          'train/target_away_rate and heatmaps/target_offset_<steps>.png + .npz under --log-dir')
+parser.add_argument('--save-shard-state', dest='save_shard_state', action='store_true',
+                    help='write the env shard and the players\' recurrent rows to <log-dir>/shard-<rank>.pt after every evaluation '
+                         'round and at exit (env snapshot blob of include/track2d_state.h, hxs, cxs, episode lengths, done flags, '
+                         'the action sampler\'s stream)')
+parser.add_argument('--load-shard-state', default=None, metavar='PATH',
+                    help='continue the shard of an earlier --save-shard-state run: a shard-<rank>.pt file, or a directory that '
+                         'holds one per rank (same --env, --num-envs, --seed, --network and --rnn-out); replaces --burn-in')
 parser.add_argument('--adv-step', type=int, default=None, metavar='AS',
                     help="--train-mode 2 only: iterations the TARGET trains before the evaluator hands back to the tracker "
                          "(test.py:88-91 of the reference reads args.adv_step, which its own main.py never defines)")
@@ -164,6 +171,20 @@ if __name__ == '__main__':
     if args.load_model_dir is not None:
         saved_state = torch.load(args.load_model_dir, map_location=lambda storage, loc: storage)
         player.model.load_state_dict(saved_state)
+    if args.load_shard_state is not None:
+        # into the player before any schedule clones its carry from it or captures a rollout over the shard; a shard of
+        # another shape or configuration ends the run here (ValueError names the field)
+        path = args.load_shard_state
+        if os.path.isdir(path):
+            path = os.path.join(path, 'shard-%d.pt' % rank)
+        player.load_shard_state(torch.load(path, map_location='cpu'))
+
+    def save_shard():
+        """--save-shard-state: after drain() and the synchronise; a schedule's carry holds what the next rollout starts from."""
+        if not args.save_shard_state:
+            return
+        os.makedirs(args.log_dir, exist_ok=True)
+        torch.save(player.shard_state(carry=getattr(sched, "carry", None)), os.path.join(args.log_dir, 'shard-%d.pt' % rank))
     # until the evaluator first speaks, the schedule of test.py:84-92 applies from iteration 0: tracker only while
     # n_iter < --init-step
     first_mode = 0 if args.init_step > 0 else args.train_mode
@@ -179,14 +200,18 @@ if __name__ == '__main__':
             sched.tune_streams()
         else:
             sched = GraphedIteration(player, optimizer, args, mode=first_mode)
-        if args.burn_in > 0 and args.load_model_dir is None:
+        if args.burn_in > 0 and args.load_model_dir is None and args.load_shard_state is None:
             # (not counted in n_steps or the logs: the updates are discarded, only the episode clocks of the shard move on)
             sched.burn_in(args.burn_in, first_mode)
             if rank == 0:
                 print("burn-in: %d iterations (%d env steps per rank) with their updates discarded"
                       % (args.burn_in, args.burn_in * args.num_steps * player.num_envs), file=sys.stderr, flush=True)
+        elif args.burn_in > 0 and rank == 0 and args.load_shard_state is not None:
+            print("burn-in skipped: the shard was restored from --load-shard-state", file=sys.stderr, flush=True)
         elif args.burn_in > 0 and rank == 0:
             print("burn-in skipped: resuming from --load-model-dir", file=sys.stderr, flush=True)
+    elif args.burn_in > 0 and rank == 0 and args.load_shard_state is not None:
+        print("burn-in skipped: the shard was restored from --load-shard-state", file=sys.stderr, flush=True)
     elif args.burn_in > 0 and rank == 0:
         print("warning: --burn-in %d ignored with --no-graph (the eager loop has no rollback of its updates)" % args.burn_in,
               file=sys.stderr, flush=True)
@@ -242,11 +267,13 @@ if __name__ == '__main__':
             if rank == 0:
                 test(args, player.model, train_modes, n_iters, rounds=1, state=eval_state)
             sync_train_modes(train_modes, device)           # rank 0 owns the schedule; a broadcast is also a barrier
+            save_shard()
             t_log, it_log = time.time(), it                 # (the evaluation's wall time is not training time)
         if it > args.max_step:
             break
     drain()
     torch.cuda.synchronize(device)
+    save_shard()
     if world > 1:       # synchronous data parallel: every rank applied the same all-reduced gradients to the same start
         flat = getattr(optimizer, "bucket", None)
         if flat is not None:
