@@ -14,7 +14,8 @@ OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libtrack2d_hip.so")
 SOURCES = ["track2d_hip.hip", "stem_hip.hip", "policy_hip.hip", "lstm_hip.hip", "heads_hip.hip", "gemm_tn_hip.hip",
            "actor_step_hip.hip", "pair_gemm_hip.hip", "bptt_hip.hip", "driver_hip.hip", "gate_cell_hip.hip", "episode_stats_hip.hip",
-           "gru_hip.hip", "render_hip.hip", "tracking_stats_hip.hip", "state_hip.hip", "np_mode.cpp", "lt_gemm.cpp"]
+           "gru_hip.hip", "render_hip.hip", "tracking_stats_hip.hip", "state_hip.hip", "stem_full_hip.hip", "np_mode.cpp",
+           "lt_gemm.cpp"]
 HEADERS = ["t2d_device.h", os.path.join("..", "..", "include", "track2d.h"),
            os.path.join("..", "..", "include", "atr_policy.h"), "atr_sample.h", "atr_cell.h",
            os.path.join("..", "..", "include", "track2d_np.h"), os.path.join("..", "..", "include", "atr_eval.h"),
@@ -22,7 +23,8 @@ HEADERS = ["t2d_device.h", os.path.join("..", "..", "include", "track2d.h"),
            os.path.join("..", "..", "include", "atr_gru_step.h"), os.path.join("..", "..", "include", "atr_gru_sums.h"),
            os.path.join("..", "..", "include", "track2d_trace.h"), "t2d_trace_view.h",
            os.path.join("..", "..", "include", "atr_track_stats.h"),
-           os.path.join("..", "..", "include", "track2d_state.h"), "t2d_state_view.h"]
+           os.path.join("..", "..", "include", "track2d_state.h"), "t2d_state_view.h",
+           os.path.join("..", "..", "include", "atr_stem_full.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wno-unused-result"]
 LDFLAGS = ["--offload-arch=gfx950", "-fPIC", "-shared", "-ldl"]
@@ -37,6 +39,8 @@ NO_SCRATCH_RENDER = {"render_hip.hip": "k_"}
 NO_SCRATCH_STATS = {"tracking_stats_hip.hip": "k_track_stats"}
 # ... and the snapshot copy (k_state_copy: at most three 16-byte pieces per lane in flight)
 NO_SCRATCH_STATE = {"state_hip.hip": "k_state_copy"}
+# ... and the whole-map stem (k_stem_full_fwd, k_stem_full_bwd, k_stem_full_reduce: w2's MFMA fragments live in 36 / 72 VGPRs)
+NO_SCRATCH_STEM_FULL = {"stem_full_hip.hip": "k_stem_full"}
 REMARKS = "-Rpass-analysis=kernel-resource-usage"
 
 
@@ -91,7 +95,7 @@ def build(force=False, verbose=False):
         if verbose:
             print(" ".join(cmd), flush=True)
         part = NO_SCRATCH.get(src) or NO_SCRATCH_LEARNER.get(src) or NO_SCRATCH_RENDER.get(src) or NO_SCRATCH_STATS.get(src)
-        part = part or NO_SCRATCH_STATE.get(src)
+        part = part or NO_SCRATCH_STATE.get(src) or NO_SCRATCH_STEM_FULL.get(src)
         if part is None:
             subprocess.check_call(cmd)
             return

@@ -10,6 +10,8 @@ every launch goes through it, so a launch status other than 0 raises RuntimeErro
                                                 the whole recurrence as one autograd node (csrc/lstm_hip.hip)
   gru_cell, gru_sequence                        the GRU cores' masked GRUCell step and their whole recurrence as one autograd
                                                 node, on the path without a rollout cache (include/atr_gru.h, csrc/gru_hip.hip)
+  stem_full                                     the same stem on the 'Full' ids' 81 / 82 wide frames (opt-in: --full-stem;
+                                                include/atr_stem_full.h, csrc/stem_full_hip.hip)
   ActionSampler                                 actor head + categorical draw (csrc/policy_hip.hip)
   gae_returns, heads_values, heads_loss         returns / GAE, critic values, heads + A3C loss terms with analytic
                                                 gradients (csrc/lstm_hip.hip, csrc/heads_hip.hip)
@@ -198,6 +200,12 @@ GRU_STEP_PROTOTYPES = {
     "atr_gru_eval_act_env_step": (C.c_int, [C.c_void_p, C.POINTER(ActStepArgs), C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p,
                                             C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
+# the whole-map ('Full' ids) conv stem, include/atr_stem_full.h (opt-in: --full-stem; held to the header by tests/test_stem_full_cpu.py)
+STEM_FULL_PROTOTYPES = {
+    "atr_stem_full_forward": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int] + [C.c_void_p] * 5 + [C.c_longlong, C.c_void_p]),
+    "atr_stem_full_workspace_floats": (C.c_longlong, [C.c_longlong]),
+    "atr_stem_full_backward": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int] + [C.c_void_p] * 10 + [C.c_longlong, C.c_void_p]),
+}
 # the library's own text for a failed launch, where it keeps one
 _ERROR_DETAIL = {"atr_act_env_step": "t2d_last_error", "atr_coop_env_step": "t2d_last_error", "atr_linear": "atr_lt_last_error"}
 _GRU_STEP_ERROR_DETAIL = {name: "t2d_last_error" for name in GRU_STEP_PROTOTYPES}
@@ -219,7 +227,8 @@ def lib():
     if _lib is None:
         L = vec_env.load_library()
         for name, (restype, argtypes, *value) in (list(ATR_PROTOTYPES.items()) + list(GRU_PROTOTYPES.items())
-                                                  + list(GRU_SUMS_PROTOTYPES.items()) + list(GRU_STEP_PROTOTYPES.items())):
+                                                  + list(GRU_SUMS_PROTOTYPES.items()) + list(GRU_STEP_PROTOTYPES.items())
+                                                  + list(STEM_FULL_PROTOTYPES.items())):
             f = getattr(L, name)
             f.restype, f.argtypes = restype, argtypes
             if restype is C.c_int and not value:
@@ -579,19 +588,27 @@ def linear_lt_set_choice(a, w, out, index, solution=-1, bias=None, relu=False, w
         raise RuntimeError("atr_linear_set_choice failed: %s" % lib().atr_lt_last_error().decode())
 
 
+def _frame_stride(x, side):
+    """The constant distance in elements between consecutive frames of x [..., side, side] when its rows are contiguous and
+    its frames evenly strided and not overlapping (one agent's slice of the env's obs tensor, or of the stacked rollout buffer);
+    None otherwise."""
+    if x.stride(-1) != 1 or x.stride(-2) != side:
+        return None
+    lead = [(sz, st) for sz, st in zip(x.shape[:-2], x.stride()[:-2]) if sz != 1]
+    stride = lead[-1][1] if lead else side * side
+    for (sz, st), (sz2, st2) in zip(lead[:-1], lead[1:]):
+        if st != sz2 * st2:
+            return None
+    return stride if stride >= side * side else None
+
+
 def rows169(x):
     """View x [..., 13, 13]-shaped frames as [M, 169] rows WITHOUT copying when the frames are evenly strided (e.g.
     one agent's slice of the env's obs tensor, or of the stacked rollout buffer); falls back to reshape (copy)."""
     m = x.numel() // 169
-    lead = [(sz, st) for sz, st in zip(x.shape[:-2], x.stride()[:-2]) if sz != 1]
-    if x.stride(-1) == 1 and x.stride(-2) == 13:
-        ok, stride = True, 169
-        if lead:
-            stride = lead[-1][1]
-            for (sz, st), (sz2, st2) in zip(lead[:-1], lead[1:]):
-                ok = ok and st == sz2 * st2
-        if ok and stride >= 169:
-            return x.as_strided((m, 169), (stride, 1), x.storage_offset())
+    stride = _frame_stride(x, 13)
+    if stride is not None:
+        return x.as_strided((m, 169), (stride, 1), x.storage_offset())
     return x.reshape(m, 169)
 
 
@@ -606,6 +623,73 @@ def _frame_rows(x):
 def stem(x, conv1, conv2):
     """x: frames [..., 13, 13] float32 on the GPU (any evenly strided view) -> [M, 512]."""
     return _Stem.apply(_frame_rows(x), conv1.weight, conv1.bias, conv2.weight, conv2.bias)
+
+
+STEM_FULL_SIDES = (81, 82)      # Maze maps, Block / Empty maps
+STEM_FULL_OUT = 32 * 21 * 21    # floats of stem output per frame, (c, h, w) order
+STEM_FULL_RECORD = 4800         # floats of one workgroup's partial record in the backward's workspace
+
+
+def stem_full_workgroup_cap():
+    """The most workgroups the whole-map stem's backward launches (three 7-row bands per frame up to this cap, then a grid stride)."""
+    return lib().atr_stem_full_workspace_floats(1 << 40) // STEM_FULL_RECORD
+
+
+def full_frames(x):
+    """View x [..., S, S]-shaped frames as [M, S, S] WITHOUT copying when rows are contiguous and the frames evenly strided (one
+    agent's planes of the env's obs tensor); a contiguous copy otherwise (stacked frames of several agents, transposed views)."""
+    S = x.shape[-1]
+    if x.dim() < 2 or x.shape[-2] != S:
+        raise ValueError("square frames expected, got %s" % (tuple(x.shape),))
+    m = x.numel() // (S * S)
+    stride = _frame_stride(x, S)
+    if stride is not None:
+        return x.as_strided((m, S, S), (stride, S, 1), x.storage_offset())
+    return x.reshape(m, S, S).contiguous()
+
+
+class _StemFull(torch.autograd.Function):
+    """CNN_maze's two convs + ReLUs on whole-map frames as one node: one launch forward, two backward (csrc/stem_full_hip.hip).
+    Saves the frames (a view), the output and the weights — conv1's activation is recomputed inside the backward kernel."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2):
+        w1c, b1c, w2c, b2c = w1.contiguous(), b1.contiguous(), w2.contiguous(), b2.contiguous()
+        M, S = x.shape[0], x.shape[-1]
+        y = torch.empty((M, STEM_FULL_OUT), dtype=torch.float32, device=x.device)
+        if M:                                        # (an empty tensor has no data pointer to hand over)
+            lib().atr_stem_full_forward(_p(x), x.stride(0), S, _p(w1c), _p(b1c), _p(w2c), _p(b2c), _p(y), M, _stream(x))
+        ctx.save_for_backward(x, y, w1c, b1c, w2c)
+        ctx.shapes = (w1.shape, w2.shape)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, y, w1, b1, w2 = ctx.saved_tensors
+        dy = dy.contiguous()
+        M, S = x.shape[0], x.shape[-1]
+        L = lib()
+        if M == 0:
+            z = lambda n: torch.zeros(n, device=x.device)
+            return None, z(144).view(ctx.shapes[0]), z(16), z(4608).view(ctx.shapes[1]), z(32)
+        ws = torch.empty(L.atr_stem_full_workspace_floats(M), dtype=torch.float32, device=x.device)
+        dw1, db1 = torch.empty(144, device=x.device), torch.empty(16, device=x.device)
+        dw2, db2 = torch.empty(4608, device=x.device), torch.empty(32, device=x.device)
+        L.atr_stem_full_backward(_p(x), x.stride(0), S, _p(y), _p(dy), _p(w1), _p(b1), _p(w2), _p(dw1), _p(db1), _p(dw2),
+                                 _p(db2), _p(ws), M, _stream(x))
+        return None, dw1.view(ctx.shapes[0]), db1, dw2.view(ctx.shapes[1]), db2
+
+
+def stem_full(x, conv1, conv2):
+    """x: single-channel frames [..., S, S], S in STEM_FULL_SIDES, float32 on the GPU (any evenly strided view is read in place)
+    -> [M, 14112], the layout `relu(conv2(relu(conv1(x)))).reshape(M, -1)` has."""
+    if not x.is_cuda or x.dtype != torch.float32:
+        raise TypeError("stem_full frames must be float32 on the GPU, got %s on %s" % (x.dtype, x.device))
+    if x.shape[-1] not in STEM_FULL_SIDES or x.shape[-2] != x.shape[-1]:
+        raise ValueError("stem_full frames must be 81 x 81 or 82 x 82, got %s" % (tuple(x.shape[-2:]),))
+    if conv1.in_channels != 1:
+        raise ValueError("stem_full reads single-channel frames")
+    return _StemFull.apply(full_frames(x), conv1.weight, conv1.bias, conv2.weight, conv2.bias)
 
 
 class ActionSampler(object):

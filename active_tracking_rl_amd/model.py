@@ -376,6 +376,9 @@ class CNN_maze(nn.Module):
         self._dense = self.dense_weights() if (on and self.small and not fused_path) else None
 
     use_fused = True   # GPU tensors go through the fused HIP stem (csrc/stem_hip.hip); set False to force GEMMs
+    # opt-in (A3C_Dueling sets it per instance from --full-stem / ATR_FULL_STEM=1): whole-map frames, 81 or 82 wide, float32 on
+    # the GPU, through the HIP stem of csrc/stem_full_hip.hip (fused.stem_full) instead of F.conv2d
+    use_fused_full = False
 
     def forward(self, x, fc=True):
         n, f = x.shape[0], x.shape[1]
@@ -383,6 +386,11 @@ class CNN_maze(nn.Module):
         if not x.is_floating_point() and not fused_ok:
             x = x.float()            # u8 observations: only the fused stem decodes them inside conv1
         if not self.small:
+            if (self.use_fused_full and x.is_cuda and x.dtype == torch.float32 and self.conv1.in_channels == 1
+                    and x.shape[-1] in (81, 82) and x.shape[-2] == x.shape[-1]):
+                from . import fused
+                x = fused.stem_full(x, self.conv1, self.conv2).reshape(n, -1)     # frames of one env side by side: [frame 0 | frame 1]
+                return F.relu(self.fc(x)) if fc else x
             return self.forward_conv2d(x, fc)
         if fused_ok:
             from . import fused
@@ -590,6 +598,11 @@ class A3C_Dueling(nn.Module):
         # env-fused one-GEMM step (k_gru_step) where new_cache's conditions hold; off = the path without a rollout cache
         # (only the value 1 turns it on: an empty ATR_FUSED_GRU, 0 or a word leave it off)
         self.fused_gru_step = bool(getattr(args, "fused_gru", False)) or __import__('os').environ.get('ATR_FUSED_GRU') == '1'
+        # opt-in (--full-stem, ATR_FULL_STEM=1; read once, here): the encoders of whole-map ('Full') ids through the HIP stem
+        self.full_stem = bool(getattr(args, "full_stem", False)) or __import__('os').environ.get('ATR_FULL_STEM') == '1'
+        for p in (self.player0, getattr(self, "player1", None)):
+            if p is not None and self.full_stem:
+                p.encoder.use_fused_full = True
 
     @property
     def cacheable_core(self):

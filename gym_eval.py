@@ -49,6 +49,9 @@ parser.add_argument('--num-steps', type=int, default=20, metavar='NS', help='env
 parser.add_argument('--fused-gru', dest='fused_gru', action='store_true',
                     help='maze-gru / tat-maze-gru: the fused one-GEMM step, which --graphed-eval needs for a GRU model '
                          '(also ATR_FUSED_GRU=1)')
+parser.add_argument('--full-stem', dest='full_stem', action='store_true',
+                    help="whole-map ('Full') ids: the encoders' two convolutions through the HIP stem for 81 / 82 wide frames "
+                         'instead of F.conv2d (also ATR_FULL_STEM=1)')
 
 if __name__ == '__main__':
     args = parser.parse_args()

@@ -65,6 +65,9 @@ parser.add_argument('--graphed-eval', dest='graphed_eval', action='store_true',
 parser.add_argument('--fused-gru', dest='fused_gru', action='store_true',
                     help='maze-gru / tat-maze-gru: the cached rollout with the env-fused one-GEMM step (k_gru_step) and the graphed '
                          'evaluator where they exist, instead of the path without a rollout cache (also ATR_FUSED_GRU=1)')
+parser.add_argument('--full-stem', dest='full_stem', action='store_true',
+                    help="whole-map ('Full') ids: the encoders' two convolutions through the HIP stem for 81 / 82 wide frames "
+                         'instead of F.conv2d (also ATR_FULL_STEM=1)')
 parser.add_argument('--env', default='Track2D-BlockPartialPZR-v0', metavar='ENV', help='environment to train on')
 parser.add_argument('--env-base', default='Track2D-BlockPartialNav-v0', metavar='ENVB', help='environment to test on ')
 parser.add_argument('--optimizer', default='Adam', metavar='OPT', help='shares optimizer choice of Adam or RMSprop')
