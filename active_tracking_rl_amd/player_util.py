@@ -52,6 +52,9 @@ class Agent(object):
         self._keep = None
         self.carry_out, self.carry_written, self._want_loss_terms = None, (), False
         self.greedy_eval = None     # (rsum, length, alive) of evaluator.GreedyEvaluator: action_rollout steps greedily
+        # (tracker, target): 'pursuit' / 'evade' replace that player's action in action_test with the heuristic player's
+        # (include/track2d_heuristic.h), None leaves it to the model
+        self.heuristic = (None, None)
         self._one = torch.ones((), dtype=torch.float32, device=device)   # seed of the backward pass (made outside any capture)
         self.done = torch.ones(self.num_envs, dtype=torch.uint8, device=device)
         self.info = None
@@ -275,7 +278,43 @@ class Agent(object):
         alive_since = torch.flip(torch.cumprod(torch.flip(nd, [0]), 0), [0])  # 1 while no done from t to the end
         self.eps_len = self.eps_len * alive_since[0] + alive_since.sum(0)
 
+    def _action_test_heuristic(self):
+        """action_test with one or both players replaced by a heuristic player: the model's actions (where a model action can
+        still reach the env — else the forward pass is skipped and the recurrent state stays as it is) with the replaced
+        columns overwritten by VecTrack2D.heuristic_actions for the state the step starts from."""
+        tracker, target = self.heuristic
+        if tracker not in (None, "pursuit") or target not in (None, "evade"):
+            raise ValueError("Agent.heuristic = %r: the tracker's entry is None or 'pursuit', the target's None or 'evade'"
+                             % (self.heuristic,))
+        core = self.env.core
+        scripted = bool(getattr(core, "scripted_target", False))       # the env ignores the target's action
+        actions = None
+        if tracker is None or (target is None and not scripted):
+            with torch.no_grad():
+                value_multi, actions, entropy, log_prob, (self.hxs, self.cxs), R_pred = self.model(
+                    (self.state, (self.hxs, self.cxs)), True)
+        if getattr(self, "_heur_act", None) is None:
+            self._heur_act = torch.zeros((self.num_envs, 2), dtype=torch.int64, device=self.device)
+        roles = tuple(r for r in (tracker, target) if r is not None)
+        core.heuristic_actions(roles, out=self._heur_act, dist=False)
+        step_actions = [self._heur_act[:, 0].contiguous() if tracker is not None else actions[0]]
+        if target is not None:
+            step_actions.append(self._heur_act[:, 1].contiguous())
+        elif actions is not None and len(actions) > 1:
+            step_actions.append(actions[1])
+        state_multi, self.reward, done, self.info = self.env.step(step_actions)
+        self.state = state_multi
+        self.done = done
+        keep = (done == 0)
+        self.eps_len = (self.eps_len + 1) * keep.to(self.eps_len.dtype)
+        k = keep.to(self.hxs.dtype).view(-1, 1, 1)
+        self.hxs = self.hxs * k
+        self.cxs = self.cxs * k
+        return self
+
     def action_test(self):
+        if self.heuristic != (None, None):
+            return self._action_test_heuristic()
         with torch.no_grad():
             value_multi, action_env_multi, entropy, log_prob, (self.hxs, self.cxs), R_pred = self.model(
                 (self.state, (self.hxs, self.cxs)), True)

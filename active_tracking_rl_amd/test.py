@@ -16,6 +16,7 @@ import time
 import numpy as np
 import torch
 
+from . import registry
 from .environment import create_env
 from .model import build_model
 from .player_util import Agent
@@ -50,15 +51,48 @@ class FrameWriter(object):
         np.savez_compressed(os.path.join(self.dir, "traces.npz"), pos=tr["pos"], len=tr["len"])
 
 
+_warned_heuristic_graphed = False
+
+
+def heuristic_players(model, env_id, heuristic_tracker=None, heuristic_target=None):
+    """The Agent.heuristic pair of an evaluation round, checked without an env: 'pursuit' may replace the tracker, 'evade' the
+    target (include/track2d_heuristic.h). model=None is accepted exactly when no model action reaches the env — the tracker is
+    heuristic and the target is heuristic or scripted by the id (Ram / Nav / RPF); else ValueError names the player without a
+    policy."""
+    if heuristic_tracker not in (None, "pursuit"):
+        raise ValueError("heuristic_tracker=%r: the heuristic tracker is 'pursuit'" % (heuristic_tracker,))
+    if heuristic_target not in (None, "evade"):
+        raise ValueError("heuristic_target=%r: the heuristic target is 'evade'" % (heuristic_target,))
+    mode = registry.spec(env_id)["target_mode"]
+    if model is None:
+        if heuristic_tracker is None:
+            raise ValueError("evaluate: no model and no heuristic_tracker: the tracker has no policy")
+        if heuristic_target is None and mode not in ("Ram", "Nav", "RPF"):
+            raise ValueError("evaluate: no model and no heuristic_target on %s, whose %s target is model-driven: the target has "
+                             "no policy" % (env_id, mode))
+    return (heuristic_tracker, heuristic_target)
+
+
 @torch.no_grad()
-def evaluate(model, env_id, args, device, episodes, seed=None, graphed=False, render_dir=None):
+def evaluate(model, env_id, args, device, episodes, seed=None, graphed=False, render_dir=None, heuristic_tracker=None,
+             heuristic_target=None):
     """Run `episodes` envs of `env_id` in parallel until each has finished ONE episode. Returns per-episode reward
     sums [episodes, 2] and lengths [episodes] (numpy). graphed: the round on the rollout's kernels as replayed hipGraphs
     (evaluator.GreedyEvaluator) where they apply, else — with one warning line — the eager round below.
     render_dir: draw the first args.render_eps episodes into it (FrameWriter). The round then runs here, on a shard without the
     in-launch auto-reset that keeps episode traces; the round ignores an env after its first done either way, so the returned
     numbers are those of a round without rendering. (A finished env of such a shard is simply stepped on from where it stands —
-    the step kernels treat it like any other env — while its trace stays closed: no masked reset is needed.)"""
+    the step kernels treat it like any other env — while its trace stays closed: no masked reset is needed.)
+    heuristic_tracker='pursuit' / heuristic_target='evade': that player's actions come from the heuristic player
+    (heuristic_players: the round is the eager one; model may be None when no model action reaches the env)."""
+    global _warned_heuristic_graphed
+    heuristic = heuristic_players(model, env_id, heuristic_tracker, heuristic_target)
+    if graphed and heuristic != (None, None):
+        if not _warned_heuristic_graphed:
+            logging.getLogger(__name__).warning("heuristic players use the eager evaluation round: the graphed step takes both "
+                                                "actions from the model")
+            _warned_heuristic_graphed = True
+        graphed = False
     if graphed and render_dir is not None:
         logging.getLogger(__name__).warning("--render uses the eager evaluation round: the graphed step restarts episodes in-launch")
         graphed = False
@@ -71,9 +105,11 @@ def evaluate(model, env_id, args, device, episodes, seed=None, graphed=False, re
     ev = create_env(env_id, args, num_envs=max(2, episodes), device=str(device),
                     env_id_base=getattr(args, "eval_env_id_base", 1 << 20), traces=render_dir is not None)
     n = ev.num_envs
-    was_training = model.training
-    model.eval()
+    was_training = model is not None and model.training
+    if model is not None:
+        model.eval()
     player = Agent(model, ev, args, None, device)
+    player.heuristic = heuristic
     player.reset()
     rsum = torch.zeros(n, player.num_agents, device=device)
     length = torch.zeros(n, dtype=torch.int32, device=device)
@@ -144,6 +180,27 @@ def save_checkpoints(model, args, n_iter, best):
     return model_dir
 
 
+def heuristic_rounds(args, model, device, writer, log, n_iter, state):
+    """--eval-heuristic: two more rounds of --test-eps episodes on args.env after an evaluation round — the model's tracker
+    against the evading target (test/vs_evade/reward0, test/vs_evade/eps_len) and the model's target against the pursuit tracker
+    (test/vs_pursuit/reward1, test/vs_pursuit/eps_len), one record per episode and one log line each. Only where args.env's
+    target is model-driven (Adv / PZR / Far); else one warning and nothing."""
+    mode = registry.spec(args.env)["target_mode"]
+    if mode in ("Ram", "Nav", "RPF"):
+        if not state.get("warned_eval_heuristic"):
+            log.warning("--eval-heuristic does nothing on {0}: its {1} target is scripted by the env".format(args.env, mode))
+            state["warned_eval_heuristic"] = True
+        return
+    for tag, col, kw in (("vs_evade", 0, dict(heuristic_target="evade")), ("vs_pursuit", 1, dict(heuristic_tracker="pursuit"))):
+        rsum, length = evaluate(model, args.env, args, device, args.test_eps, **kw)
+        for ep in range(len(length)):
+            writer.add_scalar('test/{0}/reward{1}'.format(tag, col), rsum[ep, col], n_iter)
+            writer.add_scalar('test/{0}/eps_len'.format(tag), length[ep], n_iter)
+        writer.flush()
+        log.info("{0}: ave eps reward{1} {2}, ave eps length {3}".format(
+            tag, col, rsum[:, col].sum() / args.test_eps, length.sum() / args.test_eps))
+
+
 def test(args, shared_model, train_modes, n_iters, rounds=None, state=None):
     """Evaluator loop with the reference signature. `shared_model` is the (rank-0) replica being trained; call it
     between training iterations or from a side thread. `rounds` bounds the number of evaluation rounds (None = until
@@ -192,6 +249,8 @@ def test(args, shared_model, train_modes, n_iters, rounds=None, state=None):
         if best:
             max_score = state["max_score"] = ave_reward_sum[0]
         save_checkpoints(shared_model, args, n_iter, best)
+        if getattr(args, "eval_heuristic", False):
+            heuristic_rounds(args, shared_model, device, writer, log, n_iter, state)
         done_rounds += 1
         if n_iter > args.max_step:                             # test.py:129-134
             for rank in range(len(train_modes)):

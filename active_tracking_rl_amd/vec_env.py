@@ -178,6 +178,30 @@ def state_lib():
     return _state_lib
 
 
+# ... and include/track2d_heuristic.h (the heuristic players): name -> (restype, [argtypes]); tests/test_heuristic_cpu.py holds
+# the table to the header. The result is a status.
+HEURISTIC_PROTOTYPES = {
+    "t2d_heuristic_actions": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+HEUR_PURSUIT, HEUR_EVADE = 1, 2          # T2D_HEUR_PURSUIT, T2D_HEUR_EVADE
+HEURISTIC_ROLES = {"pursuit": HEUR_PURSUIT, "evade": HEUR_EVADE}
+_heuristic_lib = None
+
+
+def heuristic_lib():
+    """The library with include/track2d_heuristic.h's prototypes declared (a library without them is an error); a non-zero
+    status raises T2DError naming the entry point, with the library's own text."""
+    global _heuristic_lib
+    if _heuristic_lib is None:
+        L = load_library()
+        for name, (restype, argtypes) in HEURISTIC_PROTOTYPES.items():
+            f = getattr(L, name)
+            f.restype, f.argtypes = restype, argtypes
+            f.errcheck = _state_errcheck(name)
+        _heuristic_lib = L
+    return _heuristic_lib
+
+
 SNAPSHOT_MAGIC = b"T2DSNAP\0"
 SNAPSHOT_VERSION = 1
 SNAPSHOT_HEADER_BYTES = 96
@@ -463,6 +487,39 @@ class VecTrack2D(object):
     def snapshot(self):
         """A new EnvSnapshot of this env (contents undefined until its first save() or load_bytes())."""
         return EnvSnapshot(self)
+
+    # -- heuristic players (include/track2d_heuristic.h) -------------------------------------------------------
+    def heuristic_actions(self, roles=("pursuit", "evade"), out=None, dist=None):
+        """(act int64 [N, 2], dist int32 [N]) for the current state of every env, in one launch: column 0 the pursuit tracker's
+        action (a shortest-path step towards the target), column 1 the evading target's (a step to the neighbouring cell
+        farthest from the tracker), dist the shortest-path distance between the two (-1: no path). roles: which columns to
+        write — the other column of `out` keeps what it held, so `out` may be a policy's own action tensor. dist=False: no
+        distances are written (None is returned in their place). Nothing of the env changes."""
+        if isinstance(roles, str):
+            roles = (roles,)
+        bits = 0
+        for r in roles:
+            if r not in HEURISTIC_ROLES:
+                raise ValueError("heuristic_actions: role %r, expected 'pursuit' and / or 'evade'" % (r,))
+            bits |= HEURISTIC_ROLES[r]
+        act = out if out is not None else torch.zeros((self.num_envs, 2), dtype=torch.int64, device=self.device)
+        assert act.is_cuda and act.dtype == torch.int64 and act.is_contiguous() and tuple(act.shape) == (self.num_envs, 2)
+        dp = None
+        if dist is False:
+            dist = None
+        else:
+            if dist is None:
+                dist = torch.empty((self.num_envs,), dtype=torch.int32, device=self.device)
+            assert dist.is_cuda and dist.dtype == torch.int32 and dist.is_contiguous() and dist.numel() == self.num_envs
+            dp = C.c_void_p(dist.data_ptr())
+        heuristic_lib().t2d_heuristic_actions(self.h, bits, C.c_void_p(act.data_ptr()), dp, self._stream())
+        return act, dist
+
+    def path_distance(self, out=None):
+        """int32 [N]: the 4-connected shortest-path distance between tracker and target over free cells, -1 without a path."""
+        if getattr(self, "_heur_act", None) is None:
+            self._heur_act = torch.zeros((self.num_envs, 2), dtype=torch.int64, device=self.device)
+        return self.heuristic_actions(("pursuit",), out=self._heur_act, dist=out)[1]
 
     # -- episode traces and the device renderer (include/track2d_trace.h) -----------------------------------
     def trace_attach(self, capacity=None):

@@ -34,6 +34,12 @@ parser.add_argument('--render-dir', default=None, metavar='DIR',
                     help='--render: folder for ep{e:03d}/step{t:04d}.png and traces.npz (default: <log-dir>/render)')
 parser.add_argument('--render-eps', type=int, default=4, metavar='K', help='--render: episodes to draw (default: 4)')
 parser.add_argument('--render-scale', type=int, default=4, metavar='S', help='--render: pixels per map cell, 1..8 (default: 4)')
+parser.add_argument('--heuristic-tracker', default=None, choices=('pursuit',),
+                    help='pursuit: the tracker walks a shortest path to the target (computed on the device) instead of following '
+                         'a checkpoint')
+parser.add_argument('--heuristic-target', default=None, choices=('evade',),
+                    help='evade: the target steps to the neighbouring cell farthest from the tracker by path length instead of '
+                         'following a checkpoint (or the id\'s own scripted target)')
 parser.add_argument('--network', default='tat-maze-lstm', metavar='M', help='Model type to use')
 parser.add_argument('--stack-frames', type=int, default=1, metavar='SF', help='Choose whether to stack observations')
 parser.add_argument('--seed', type=int, default=1, metavar='S', help='random seed (default: 1)')
@@ -80,7 +86,8 @@ if __name__ == '__main__':
         model.player1.load_state_dict(load(args.load_target))             # :88-92
     args.gpu_ids = [device.index]
     render_dir = (args.render_dir or os.path.join(args.log_dir, 'render')) if args.render else None
-    rsum, length = evaluate(model, args.env, args, device, args.num_episodes, graphed=args.graphed_eval, render_dir=render_dir)
+    rsum, length = evaluate(model, args.env, args, device, args.num_episodes, graphed=args.graphed_eval, render_dir=render_dir,
+                            heuristic_tracker=args.heuristic_tracker, heuristic_target=args.heuristic_target)
     reward_mean, reward_std = rsum.mean(0), rsum.std(0)
     len_mean, len_std = length.mean(), length.std()
     success_rate = float((length >= 500).mean())

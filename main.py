@@ -86,6 +86,11 @@ parser.add_argument('--rescale', dest='rescale', action='store_true', help='resc
 parser.add_argument('--render', dest='render', action='store_true',
                     help='draw the first --render-eps episodes of every test round on the device and write them as PNG frames '
                          'under <log-dir>/render/iter{n}/ (such rounds run eagerly on a shard that keeps episode traces)')
+parser.add_argument('--eval-heuristic', dest='eval_heuristic', action='store_true',
+                    help='after every evaluation round, two more rounds of --test-eps episodes on --env against the heuristic '
+                         'players: the tracker against the evading target (test/vs_evade/reward0, test/vs_evade/eps_len) and the '
+                         'target against the pursuit tracker (test/vs_pursuit/reward1, test/vs_pursuit/eps_len); only where '
+                         "--env's target is model-driven (Adv / PZR / Far)")
 parser.add_argument('--render-eps', type=int, default=4, metavar='K', help='--render: episodes to draw per test round (default: 4)')
 parser.add_argument('--render-scale', type=int, default=4, metavar='S', help='--render: pixels per map cell, 1..8 (default: 4)')
 parser.add_argument('--shared-optimizer', dest='shared_optimizer', action='store_true',
