@@ -897,8 +897,28 @@ def _lstm_bptt(whh, keep, h_all, c_all, acts, dhs, whh_nn=None, want_dwhh=True, 
                             for p in range(P)], 0)
     else:
         hm = (h_all[:, :T] * kprev.view(1, T, N, 1)).view(P, T * N, R)
-        dwhh = torch.bmm(hm.transpose(1, 2), dG)
+        dwhh = bmm_tn(hm, dG)
     return dG, dhn, dcc, dwhh
+
+
+BMM_TN_CHUNK = 512
+
+
+def bmm_tn(a, b):
+    """a^T b per batch for tall a [P, K, M], b [P, K, N] — dW_hh where gemm_tn does not take the shape (R no multiple of 128).
+    From 4096 rows up (gemm_tn's own threshold) as partial products over chunks of BMM_TN_CHUNK rows, summed in a second step:
+    the library product's one running fp32 sum over K = 4096 rows was measured at e = 1.2e-6 against float64 (R = 64, 1024 envs
+    x 4 steps, tests/test_learner_f64_gpu.py), four times the error of PyTorch's own fp32 evaluation of the same gradient."""
+    P, K, M = a.shape
+    C = K // BMM_TN_CHUNK
+    if K < 4096:
+        return torch.bmm(a.transpose(1, 2), b)
+    Kc = C * BMM_TN_CHUNK
+    out = torch.bmm(a[:, :Kc].reshape(P * C, BMM_TN_CHUNK, M).transpose(1, 2),
+                    b[:, :Kc].reshape(P * C, BMM_TN_CHUNK, b.shape[2])).view(P, C, M, b.shape[2]).sum(1)
+    if Kc < K:
+        out = out + torch.bmm(a[:, Kc:].transpose(1, 2), b[:, Kc:])
+    return out
 
 
 def gru_cell(ig, hg, b_hh, h_prev, keep=None, done=None):

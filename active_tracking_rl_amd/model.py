@@ -63,8 +63,46 @@ def weights_init_mlp(m):
         m.bias.zero_()
 
 
+HEADS_LANES = (16, 32, 64)   # csrc/heads_hip.hip holds a row's R = 4 L hidden units in L lanes of one wave: R = 64, 128, 256
+SAMPLER_MAX_R = 256          # csrc/policy_hip.hip, kMaxR: the longest hidden row the action-draw kernels take
+BOOT_MAX_R = 128             # the largest size whose bootstrap value comes from one more step of the rollout's cell kernels
+
+
+def hidden_size_support(R):
+    """Which of the GPU fast paths exist for hidden size R (--rnn-out) — the ONE predicate every gate asks:
+      cache          the rollout cache and the cell kernels (new_cache): R a multiple of 4
+      fused_heads    heads + loss terms as HIP nodes (Agent._loss_fused_heads, boot_values): R / 4 lanes per row in HEADS_LANES;
+                     otherwise the learner evaluates the heads with tensor ops (forward_sequence_cached) and the bootstrap value
+                     with the model's own forward
+      fused_boot     the learner's bootstrap value V(s_T) through one more step of the rollout's kernels (boot_values): the sizes
+                     with fused heads up to BOOT_MAX_R. At R = 256 that step's values missed the float64 rule of
+                     tests/test_learner_f64_gpu.py in the eager case (e = 1.32e-6 against 1.23e-6 allowed; the captured case kept
+                     it by 2 %), so R = 256 takes the model's own forward for that one step: measured there 5.8e-7 eager and
+                     4.7e-7 captured. The cause is inferred, not shown: the stored hidden rows of that size carry e = 1.2e-6 ..
+                     1.8e-6 (6e-7 .. 1.1e-6 at R = 64), which fits csrc/atr_cell.h's ~1e-7 absolute tanh on the smaller states of
+                     a wider cell. The cost — an encoder, two LSTMCell calls and a draw in place of one fused step, once per
+                     iteration — has not been timed
+      fused_sampler  the action draw (fused.ActionSampler, every rollout step on the GPU): R a multiple of 4 up to SAMPLER_MAX_R;
+                     there is no other draw under a captured rollout, so a GPU model of any other size is refused when it is
+                     built (check_hidden_size)."""
+    R = int(R)
+    quad = R > 0 and R % 4 == 0
+    heads = quad and R // 4 in HEADS_LANES
+    return dict(cache=quad, fused_heads=heads, fused_boot=heads and R <= BOOT_MAX_R, fused_sampler=quad and R <= SAMPLER_MAX_R)
+
+
+def check_hidden_size(R, device):
+    """ValueError for a hidden size the GPU rollout has no action draw for — raised where the model is built, before any launch."""
+    if device is None or torch.device(device).type != 'cuda' or hidden_size_support(R)["fused_sampler"]:
+        return
+    raise ValueError("--rnn-out %d is not supported on the GPU: the rollout's action-draw kernels take hidden sizes that are "
+                     "multiples of 4 up to %d (the fused heads and loss: %s; other such sizes evaluate the heads with tensor ops)"
+                     % (int(R), SAMPLER_MAX_R, ", ".join(str(4 * l) for l in HEADS_LANES)))
+
+
 def build_model(obs_space, action_space, args, device):
     """Same signature as the reference build_model (model.py:12-15)."""
+    check_hidden_size(args.rnn_out, device)
     model = A3C_Dueling(obs_space, action_space, args, device)
     model.train()
     return model
@@ -577,6 +615,7 @@ class A3C_Dueling(nn.Module):
         obs_shapes = [obs_space[i].shape for i in range(self.num_agents)]
         stack_frames = args.stack_frames
         rnn_out = args.rnn_out
+        check_hidden_size(rnn_out, device)
         head_name = args.network
         self.single = args.single
         self.device = device
@@ -767,7 +806,7 @@ class A3C_Dueling(nn.Module):
         ok = (states.is_cuda and states.dtype in (torch.float32, torch.uint8) and fused_lstm and not self.single
               and all(isinstance(p.encoder, CNN_maze) and p.encoder.small and p.encoder.use_fused
                       and p.encoder.conv1.in_channels == 1 for p in (p0, p1))
-              and states.shape[-1] == 13 and states.shape[-2] == 13 and p0.lstm.hidden_size % 4 == 0
+              and states.shape[-1] == 13 and states.shape[-2] == 13 and hidden_size_support(p0.lstm.hidden_size)["cache"]
               and p0.lstm.hidden_size == p1.lstm.hidden_size)
         if not ok:
             return None
@@ -955,6 +994,9 @@ class A3C_Dueling(nn.Module):
         state of slot T into scratch buffers (the tracker's action is drawn, as the reference's forward draws it, because
         the tracker-aware target's features depend on it), then the critic heads. v_out [N, A, 1] float32 contiguous."""
         from . import fused
+        if not hidden_size_support(cache.h_all.shape[-1])["fused_boot"]:
+            raise ValueError("boot_values takes hidden sizes %s (hidden_size_support): the bootstrap value of other sizes comes "
+                             "from the model's own forward" % ", ".join(str(4 * l) for l in HEADS_LANES if 4 * l <= BOOT_MAX_R))
         b = getattr(cache, "boot", None)
         if b is None:
             b = cache.boot = RolloutCache()

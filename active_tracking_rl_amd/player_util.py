@@ -471,9 +471,14 @@ class Agent(object):
             states = torch.stack(self.states, 0)
             rewards = torch.stack(self.rewards, 0)                           # [T, N, A, 1]
             nd = (torch.stack(self.dones, 0) == 0).to(rewards.dtype)         # [T, N]
-        if self._cache is not None and T == self._cache.T and self.fused_heads:
-            return self._loss_fused_heads(training_mode, states, actions, rewards, nd)
-        if self._cache is not None and T == self._cache.T:
+        cached = self._cache is not None and T == self._cache.T
+        if cached and self.fused_heads:
+            # (the heads kernels exist for some hidden sizes only: model.hidden_size_support; every other cached size takes the
+            # tensor heads below, with the recurrence still back-propagated over the rollout's stored activations)
+            from .model import hidden_size_support
+            if hidden_size_support(self._cache.h_all.shape[-1])["fused_heads"]:
+                return self._loss_fused_heads(training_mode, states, actions, rewards, nd)
+        if cached:
             values, entropies, log_probs, preds = self.model.forward_sequence_cached(self._cache, states, actions, nd)
         else:
             values, entropies, log_probs, preds = self.model.forward_sequence(states, actions, self.h0, self.c0, nd)
@@ -535,7 +540,9 @@ class Agent(object):
                 for p in range(A):
                     fused.heads_values(h_seq[p].detach().reshape(T * N, R_dim), players[p].critic.critic_linear, v, p)
             sampler = getattr(model, "_sampler", None)
-            if hasattr(model, "boot_values") and sampler is not None and getattr(sampler, "_last", None) is not None:
+            from .model import hidden_size_support
+            if (hasattr(model, "boot_values") and sampler is not None and getattr(sampler, "_last", None) is not None
+                    and hidden_size_support(R_dim)["fused_boot"]):
                 sampler.reopen_block()       # V(s_T) with the rollout's kernels: one more actor step + the critic heads
                 model.boot_values(self.state, self._cache, self.done, v[T])
                 sampler.end_block()

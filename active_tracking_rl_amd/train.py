@@ -52,6 +52,8 @@ def select_params(model, train_mode):
 
 def make_player(args, device, rank=0, world_size=1, env=None, model=None, optimizer=None):
     """Build env shard + replica + optimizer + Agent for one rank."""
+    from .model import check_hidden_size
+    check_hidden_size(args.rnn_out, device)   # (a model handed in was built elsewhere: the same refusal, before any launch)
     if device.type == 'cuda':
         from . import gemm_tuning
         gemm_tuning.enable()                  # read-only TunableOp picks for the policy GEMMs (no-op without the file)

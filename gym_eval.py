@@ -47,7 +47,7 @@ parser.add_argument('--gpu-id', type=int, default=0, help='GPU to use')
 parser.add_argument('--obs', default='img', metavar='UE', help='unreal env')
 parser.add_argument('--single', dest='single', action='store_true', help='single agent')
 parser.add_argument('--rescale', dest='rescale', action='store_true', help='rescale image to [-1, 1]')
-parser.add_argument('--rnn-out', type=int, default=128, metavar='LO', help='lstm output size')
+parser.add_argument('--rnn-out', type=int, default=128, metavar='LO', help='lstm output size: on the GPU a multiple of 4 up to 256')
 parser.add_argument('--aux', default='reward', help='auxiliary task: reward/none')
 parser.add_argument('--graphed-eval', dest='graphed_eval', action='store_true',
                     help='run the episodes on the rollout kernels as replayed hipGraphs where the env allows it')

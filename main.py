@@ -99,7 +99,7 @@ parser.add_argument('--split', dest='split', action='store_true', help='split mo
 parser.add_argument('--train-mode', type=int, default=-1, metavar='TM', help='which agent to train(0:tracker 1:target)')
 parser.add_argument('--stack-frames', type=int, default=1, metavar='SF', help='Choose number of observations to stack')
 parser.add_argument('--input-size', type=int, default=80, metavar='IS', help='input image size')
-parser.add_argument('--rnn-out', type=int, default=128, metavar='LO', help='rnn output size')
+parser.add_argument('--rnn-out', type=int, default=128, metavar='LO', help='rnn output size: on the GPU a multiple of 4 up to 256 (64, 128, 256 run every kernel)')
 parser.add_argument('--sleep-time', type=int, default=0, metavar='ST', help='accepted for compatibility')
 parser.add_argument('--max-step', type=int, default=150000, metavar='MS', help='max learning steps (iterations)')
 parser.add_argument('--init-step', type=int, default=-1, metavar='IS', help='steps not update target at beginning')

@@ -87,7 +87,7 @@ def test_fused_action_sampler_draws_from_the_softmax_distribution():
     assert abs(mean_p - expect) < 0.01, (mean_p, expect)
 
 
-def test_fused_lstm_sequence_matches_the_aten_recurrence():
+def _lstm_sequence_against_the_aten_recurrence():
     """csrc/lstm_hip.hip (one autograd node for the masked two-player recurrence) against the per-step ATen path:
     outputs, final state and every gradient (fp32; tolerances cover sigmoid/tanh implementation differences)."""
     from active_tracking_rl_amd import model as M
@@ -121,6 +121,66 @@ def test_fused_lstm_sequence_matches_the_aten_recurrence():
     for a, b in zip(g_a, g_b):
         scale = float(b.abs().max()) + 1e-6
         assert float((a - b).abs().max()) <= 2e-4 * scale, (a.shape, float((a - b).abs().max()), scale)
+
+
+# (reference, R, P, N, T, fused.use_fused_bptt). "aten": the fp32 comparison above at the shapes it always had. "f64": the rule of
+# tests/f64_rule.py against a float64 per-step nn.LSTMCell recurrence. R = 128 takes the one-launch BPTT (csrc/bptt_hip.hip) or,
+# with the switch off, the per-step path (atr_lstm_cell_backward + bmm) that every other R takes in production; R = 96 is a size
+# without a heads kernel whose cells still run; 256 x 512 x 8 = 4096 rows sends dW_hh through gemm_tn with row_scale (M = 256,
+# N = 1024).
+LSTM_CASES = ([("aten", 128, 2, 37, 7, True)] +
+              [("f64", R, P, N, 7, True) for R in (64, 96, 128, 256) for P in (1, 2) for N in (1, 37)] +
+              [("f64", 128, P, N, 7, False) for P in (1, 2) for N in (1, 37)] +
+              [("f64", 256, 2, 512, 8, True)])
+
+
+@pytest.mark.parametrize("ref,R,P,N,T,fused_bptt", LSTM_CASES)
+def test_fused_lstm_sequence_matches_the_aten_recurrence(ref, R, P, N, T, fused_bptt, monkeypatch):
+    """model.lstm_sequence on the HIP recurrence (csrc/lstm_hip.hip; backward: csrc/bptt_hip.hip at R = 128, else
+    atr_lstm_cell_backward + bmm per step) against the same masked recurrence through nn.LSTMCell in float64: outputs, final
+    state, and the gradients to the features, h0, c0 and every weight and bias.
+    Measured on MI355X over the f64 cases (per-step backward: R = 64 / 96 / 256 and R = 128 with the switch off | one launch):
+      h_seq, h_fin, c_fin   e(hip) 0 .. 3.5e-07 | 0 .. 3.2e-07          e(aten32) 0 .. 3.3e-07         e(hip) / allowed <= 0.09
+      weight_ih             e(hip) 1.7e-07 .. 1.1e-06 | .. 3.9e-07      e(aten32) 1.5e-07 .. 4.6e-07   e(hip) / allowed <= 0.61
+      weight_hh             e(hip) 1.8e-07 .. 5.2e-07 | .. 4.4e-07      e(aten32) 1.6e-07 .. 5.3e-07   e(hip) / allowed <= 0.39
+      bias_ih, bias_hh      e(hip) 1.5e-07 .. 3.5e-07 | .. 2.8e-07      e(aten32) 1.3e-07 .. 3.0e-07   e(hip) / allowed <= 0.29
+      feats, h0, c0         e(hip) 1.1e-07 .. 5.8e-07 | .. 4.6e-07      e(aten32) 9.2e-08 .. 5.1e-07   e(hip) / allowed <= 0.42
+    (weight_ih's 1.1e-06 is the 4096-row case: that product is torch's own, the backward of F.linear.)"""
+    if ref == "aten":
+        return _lstm_sequence_against_the_aten_recurrence()
+    from f64_rule import HIDDEN_FLOOR, Table, cell_recurrence
+    from active_tracking_rl_amd import fused, model as M
+    torch.manual_seed(R + 2 * P + N)
+    Fdim = 256
+    lstms = [torch.nn.LSTMCell(Fdim, R).cuda() for _ in range(P)]
+    feats = torch.randn(T, P, N, Fdim, device="cuda", requires_grad=True)
+    h0 = torch.randn(P, N, R, device="cuda", requires_grad=True)
+    c0 = torch.randn(P, N, R, device="cuda", requires_grad=True)
+    keep = (torch.rand(T, N, device="cuda") > 0.3).float()
+    go, gh = torch.randn(T, P, N, R, device="cuda"), torch.randn(P, N, R, device="cuda")
+    calls = []
+    gemm_tn = fused.gemm_tn
+    monkeypatch.setattr(fused, "gemm_tn", lambda *a, **k: (calls.append((a[0].shape, a[1].shape, k.get("row_scale") is not None)),
+                                                           gemm_tn(*a, **k))[1])
+    monkeypatch.setattr(fused, "use_fused_bptt", fused_bptt)
+    names = ["%s[%d]" % (n, p) for p in range(P) for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")] + ["feats", "h0", "c0"]
+    wrt = [getattr(lstms[p], n) for p in range(P) for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")] + [feats, h0, c0]
+    h_seq, h_fin, c_fin = M.lstm_sequence(lstms, [feats[:, p] for p in range(P)], h0, c0, keep)
+    assert isinstance(h_seq, list) and h_seq[0].shape == (T, N, R)              # the HIP recurrence, not the ATen form
+    h_seq = torch.stack(h_seq, 1)
+    grads = dict(zip(names, torch.autograd.grad((h_seq * go).sum() + (h_fin * gh).sum(), wrt)))
+    if T * N >= 4096:
+        assert calls == [((T * N, R), (T * N, 4 * R), True)] * P, calls         # dW_hh: gemm_tn with the mask as row_scale
+    else:
+        assert not calls
+    x64 = cell_recurrence(lstms, feats, h0, c0, keep, go, gh, torch.float64, "cpu")
+    x32 = cell_recurrence(lstms, feats, h0, c0, keep, go, gh, torch.float32, "cuda")
+    tab = Table("lstm R=%d P=%d N=%d T=%d bptt=%s" % (R, P, N, T, "one-launch" if (fused_bptt and R == 128) else "per-step"))
+    for what, got in (("h_seq", h_seq), ("h_fin", h_fin), ("c_fin", c_fin)):
+        tab.rule(what, got, x64[what], x32[what], floor=HIDDEN_FLOOR)
+    for n in names:
+        tab.rule(n, grads[n], x64[n], x32[n])
+    tab.finish()
 
 
 def test_fused_lstm_single_player_and_rollout_cell():
@@ -159,23 +219,26 @@ def test_fused_lstm_single_player_and_rollout_cell():
         torch.testing.assert_close(a, b, rtol=1e-4, atol=2e-5)
 
 
-def test_gae_kernel_matches_the_reference_recursion():
+@pytest.mark.parametrize("gamma,tau", [(0.9, 1.0), (0.99, 0.95), (0.5, 0.0)])
+def test_gae_kernel_matches_the_reference_recursion(gamma, tau):
+    """k_gae against the recursion of player_util.py:118-141 of the reference evaluated in float64 (tau != 1 and tau = 0: a
+    kernel that dropped the tau factor would pass at tau = 1 only)."""
     from active_tracking_rl_amd import fused
     torch.manual_seed(5)
     T, N, A = 20, 300, 2
     rew = torch.randn(T, N, A, 1, device="cuda")
     val = torch.randn(T + 1, N, A, 1, device="cuda")
     nd = (torch.rand(T, N, device="cuda") > 0.1).float()
-    gamma, tau = 0.9, 1.0
     R, gae = fused.gae_returns(rew, val, nd, gamma, tau)
-    ndv = nd.view(T, N, 1, 1)
-    r_run, g_run = val[T], torch.zeros_like(val[T])
+    rew64, val64 = rew.double(), val.double()
+    ndv = nd.double().view(T, N, 1, 1)
+    r_run, g_run = val64[T], torch.zeros_like(val64[T])
     for i in reversed(range(T)):                              # player_util.py:118-141 of the reference
-        r_run = gamma * r_run * ndv[i] + rew[i]
-        delta_t = rew[i] + gamma * val[i + 1] * ndv[i] - val[i]
+        r_run = gamma * r_run * ndv[i] + rew64[i]
+        delta_t = rew64[i] + gamma * val64[i + 1] * ndv[i] - val64[i]
         g_run = g_run * gamma * tau * ndv[i] + delta_t
-        torch.testing.assert_close(R[i], r_run, rtol=1e-6, atol=1e-6)
-        torch.testing.assert_close(gae[i], g_run, rtol=1e-6, atol=1e-6)
+        torch.testing.assert_close(R[i].double(), r_run, rtol=1e-6, atol=1e-6)
+        torch.testing.assert_close(gae[i].double(), g_run, rtol=1e-6, atol=1e-6)
 
 
 @pytest.mark.parametrize("M0,M1", [(4096, 8192), (5, 3), (1, 700), (4096, 4096), (3100, 5), (9, 8183), (2048, 4096)])

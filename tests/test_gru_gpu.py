@@ -104,6 +104,48 @@ def test_gru_sequence_node_matches_float64(fused_bptt):
         assert float((dbi[2 * R:] - dbh[2 * R:]).abs().max()) > 1e-2 * float(dbi[2 * R:].abs().max())
 
 
+@pytest.mark.parametrize("N", [1, 37])
+@pytest.mark.parametrize("P", [1, 2])
+@pytest.mark.parametrize("R", [64, 256])
+def test_gru_sequence_node_at_other_hidden_sizes_matches_float64(R, P, N):
+    """model.gru_sequence off R = 128 (--rnn-out): the cell kernel forward and, as there is no one-launch BPTT off 128, the
+    per-step backward (atr_gru_cell_backward + baddbmm) that such models train through, by the rule of tests/f64_rule.py
+    against a float64 per-step nn.GRUCell recurrence: outputs, final state, gradients to the features, h0 and every weight and
+    bias. Measured on MI355X over the eight cases:
+      h_seq, h_fin          e(hip) 0 .. 2.8e-07         e(aten32) 0 .. 2.7e-07         e(hip) / allowed <= 0.07
+      weight_ih, weight_hh  e(hip) 1.5e-07 .. 4.5e-07   e(aten32) 1.4e-07 .. 4.1e-07   e(hip) / allowed <= 0.35
+      bias_ih, bias_hh      e(hip) 1.2e-07 .. 3.2e-07   e(aten32) 1.1e-07 .. 3.1e-07   e(hip) / allowed <= 0.30
+      feats, h0             e(hip) 8.6e-08 .. 4.1e-07   e(aten32) 1.2e-07 .. 3.7e-07   e(hip) / allowed <= 0.27"""
+    from f64_rule import HIDDEN_FLOOR, Table, cell_recurrence
+    from active_tracking_rl_amd import model as M
+    dev = _dev()
+    torch.manual_seed(R + 2 * P + N)
+    T, Fd = 7, 256
+    cells = [nn.GRUCell(Fd, R).to(dev) for _ in range(P)]
+    with torch.no_grad():
+        for c in cells:                     # zero biases would hide a wrong b_hn path
+            c.bias_ih.normal_(0, 0.5); c.bias_hh.normal_(0, 0.5)
+    feats = torch.randn(T, P, N, Fd, device=dev, requires_grad=True)
+    h0 = (torch.randn(P, N, R, device=dev) * 0.5).requires_grad_(True)
+    keep = (torch.rand(T, N, device=dev) > 0.3).float()
+    go, gh = torch.randn(T, P, N, R, device=dev), torch.randn(P, N, R, device=dev)
+    names = ["%s[%d]" % (n, p) for p in range(P) for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")] + ["feats", "h0"]
+    wrt = [getattr(cells[p], n) for p in range(P) for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")] + [feats, h0]
+    h_seq, h_fin, c_fin = M.gru_sequence(cells, [feats[:, p] for p in range(P)], h0, torch.zeros(P, N, R, device=dev), keep)
+    assert isinstance(h_seq, list) and h_seq[0].shape == (T, N, R)              # the HIP recurrence, not the ATen fallback
+    h_seq = torch.stack(h_seq, 1)
+    grads = dict(zip(names, torch.autograd.grad((h_seq * go).sum() + (h_fin * gh).sum(), wrt)))
+    x64 = cell_recurrence(cells, feats, h0, None, keep, go, gh, torch.float64, "cpu")
+    x32 = cell_recurrence(cells, feats, h0, None, keep, go, gh, torch.float32, dev)
+    tab = Table("gru R=%d P=%d N=%d T=%d" % (R, P, N, T))
+    tab.rule("h_seq", h_seq, x64["h_seq"], x32["h_seq"], floor=HIDDEN_FLOOR)
+    tab.rule("h_fin", h_fin, x64["h_fin"], x32["h_fin"], floor=HIDDEN_FLOOR)
+    for n in names:
+        tab.rule(n, grads[n], x64[n], x32[n])
+    tab.finish()
+    assert float(c_fin.abs().max()) == 0.0
+
+
 @pytest.mark.parametrize("N,P,T", [(16, 1, 1), (37, 1, 5), (40, 2, 3), (512, 2, 20)])
 def test_one_launch_gru_bptt_matches_the_per_step_path(N, P, T):
     from active_tracking_rl_amd import fused
