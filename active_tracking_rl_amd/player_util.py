@@ -340,6 +340,9 @@ class Agent(object):
         track = getattr(self.env, "tracking_stats", None)     # (tracking_stats.TrackingStats: the next action pairs with no state)
         if track is not None:
             track.reset_running()
+        sight = getattr(self.env, "sight_stats", None)        # (sight_stats.SightStats: the next sample follows no state)
+        if sight is not None:
+            sight.reset_running()
 
     # -- the shard as a file (main.py --save-shard-state / --load-shard-state) ---------------------------------------
     def _shard_meta(self):

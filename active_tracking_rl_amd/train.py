@@ -111,6 +111,14 @@ def rollout(player, num_steps, fast=True):
         acts = getattr(player, "_actions_buf", None)
         acts = acts.permute(0, 2, 1) if acts is not None else torch.stack(player.actions[-num_steps:])
         track.update(buf[0], buf[1], buf[2], acts)
+    # sight statistics (sight_stats.SightStats, opt-in, attached to the env shard in the same way, with a carry and a table of their
+    # own): one launch over the windows, rewards and done flags of the rollout store.
+    sight = getattr(player.env, "sight_stats", None)
+    if sight is not None:
+        buf = player._buf if fast else None
+        if buf is None or buf[2].shape[0] != num_steps:
+            raise RuntimeError("sight statistics read the rollout store, and this rollout has none (fast=%s)" % fast)
+        sight.update(buf[0], buf[1], buf[2])
     # A rollout that is not a whole number of generator stamp cycles restarts the stamps (so that a captured rollout
     # replays consistently); otherwise forked generator launches stay in flight under the learner's kernels.
     if hasattr(player.env, "flush") and num_steps % getattr(player.env, "generator_cycle", 1) != 0:
@@ -818,6 +826,10 @@ def train(rank, args, shared_model, optimizer, train_modes, n_iters, env=None):
     if getattr(args, "tracking_stats", False):
         from .tracking_stats import TrackingStats
         track = TrackingStats(player.env, device)
+    sight = None
+    if getattr(args, "sight_stats", False):
+        from .sight_stats import SightStats
+        sight = SightStats(player.env, device)
     n_iter = 0
     try:
         while True:
@@ -837,6 +849,8 @@ def train(rank, args, shared_model, optimizer, train_modes, n_iters, env=None):
                     ep_stats.record(writer, player.n_steps, rank)
                 if track is not None:
                     track.record(writer, player.n_steps, rank, args.log_dir)
+                if sight is not None:
+                    sight.record(writer, player.n_steps, rank, args.log_dir)
                 writer.flush()
             if train_modes[rank] == -100 or n_iter * world > args.max_step:   # test.py:129-134 stop rule
                 break

@@ -125,6 +125,11 @@ parser.add_argument('--tracking-stats', dest='tracking_stats', action='store_tru
                          'from there (one more launch per rollout); every --log-every record writes train/in_view_rate, '
                          'train/in_range_rate, train/colocated_rate, train/mean_distance, train/tracker_toward_rate, '
                          'train/target_away_rate and heatmaps/target_offset_<steps>.png + .npz under --log-dir')
+parser.add_argument('--sight-stats', dest='sight_stats', action='store_true',
+                    help='count on the device whether the tracker\'s line of sight to the target is clear or blocked by a wall, how '
+                         'long the shortest way round inside its window is, and how often sight is lost to a wall or to range and '
+                         'regained (one more launch per rollout); every --log-every record writes the train/sight_* scalars and '
+                         'heatmaps/occlusion_<steps>.png + .npz under --log-dir')
 parser.add_argument('--save-shard-state', dest='save_shard_state', action='store_true',
                     help='write the env shard and the players\' recurrent rows to <log-dir>/shard-<rank>.pt after every evaluation '
                          'round and at exit (env snapshot blob of include/track2d_state.h, hxs, cxs, episode lengths, done flags, '
@@ -176,6 +181,10 @@ if __name__ == '__main__':
     if args.tracking_stats:
         from active_tracking_rl_amd.tracking_stats import TrackingStats
         track_stats = TrackingStats(player.env, device)
+    sight_stats = None
+    if args.sight_stats:
+        from active_tracking_rl_amd.sight_stats import SightStats
+        sight_stats = SightStats(player.env, device)
     if args.load_model_dir is not None:
         saved_state = torch.load(args.load_model_dir, map_location=lambda storage, loc: storage)
         player.model.load_state_dict(saved_state)
@@ -223,7 +232,7 @@ if __name__ == '__main__':
     elif args.burn_in > 0 and rank == 0:
         print("warning: --burn-in %d ignored with --no-graph (the eager loop has no rollback of its updates)" % args.burn_in,
               file=sys.stderr, flush=True)
-    if (ep_stats is not None or track_stats is not None) and sched is not None:
+    if (ep_stats is not None or track_stats is not None or sight_stats is not None) and sched is not None:
         # warm-up iterations, tune_streams trials and burn-in moved the shard on without being training: the episodes they
         # finished (the samples they counted) are drained and dropped; the episodes in flight carry on and are counted whole
         # when they end
@@ -233,6 +242,8 @@ if __name__ == '__main__':
             ep_stats.drain()
         if track_stats is not None:
             track_stats.drain()
+        if sight_stats is not None:
+            sight_stats.drain()
     step = sched.run if sched is not None else None
     drain = getattr(sched, "finish", lambda: None)          # pipelined: both streams joined before the host reads anything
     it = 0
@@ -267,6 +278,8 @@ if __name__ == '__main__':
                 ep_stats.record(writer, it * args.num_steps * player.num_envs, rank)
             if track_stats is not None:
                 track_stats.record(writer, it * args.num_steps * player.num_envs, rank, args.log_dir)
+            if sight_stats is not None:
+                sight_stats.record(writer, it * args.num_steps * player.num_envs, rank, args.log_dir)
             writer.flush()
             t_log, it_log = time.time(), it
         if it % args.test_every == 0 or it > args.max_step:

@@ -2,7 +2,8 @@
 tools/summarize_prof.py; `calls / ITERS` and `total / ITERS` are per iteration (plus two eager warm-up iterations).
   python tools/iter_profile.py [ITERS] [env] [num_envs] [network] [aux] [train_mode]      (default: the headline config)
 ITER_PROFILE_SCHEDULE=pipelined profiles the two-stream schedule instead (kernel durations BESIDE the other chain).
-ITER_PROFILE_TRACKING_STATS=1 attaches tracking_stats.TrackingStats to the shard (k_track_stats: one launch per rollout)."""
+ITER_PROFILE_TRACKING_STATS=1 attaches tracking_stats.TrackingStats to the shard (k_track_stats: one launch per rollout).
+ITER_PROFILE_SIGHT_STATS=1 attaches sight_stats.SightStats to the shard (k_sight_stats: one launch per rollout)."""
 import os
 import sys
 import torch
@@ -17,6 +18,9 @@ player, opt = make_player(args, dev)
 if os.environ.get("ITER_PROFILE_TRACKING_STATS") == "1":
     from active_tracking_rl_amd.tracking_stats import TrackingStats
     TrackingStats(player.env, dev)
+if os.environ.get("ITER_PROFILE_SIGHT_STATS") == "1":
+    from active_tracking_rl_amd.sight_stats import SightStats
+    SightStats(player.env, dev)
 if os.environ.get("ITER_PROFILE_SCHEDULE") == "pipelined":
     it = PipelinedIteration(player, opt, args)
     it.tune_streams()
