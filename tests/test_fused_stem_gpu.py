@@ -1,6 +1,7 @@
 """-m gpu numerics test of the fused HIP conv stem (csrc/stem_hip.hip) against the plain PyTorch fp32 reference of
 the same op (F.conv2d + ReLU, autograd for the gradients). Tolerances: forward 1e-5 abs/rel; parameter gradients
-2e-4 relative to the gradient's max (fp32 sums over up to 10^5 frames in a different order)."""
+2e-4 relative to the gradient's max (fp32 sums over up to 10^5 frames in a different order). The stem's comparison with float64
+(bit-exact on integer frames, every kernel form and loop trip) is tests/test_stem_f64_gpu.py's."""
 import numpy as np
 import pytest
 import torch
