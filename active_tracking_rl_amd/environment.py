@@ -45,12 +45,17 @@ def _spaces(obs_hw=(13, 13), num_actions=4):
     return obs, act
 
 
+def _obs_type(env_id, overrides):
+    """'Partial' / 'Full' as VecTrack2D will decide it: the id's, else the obs_type override's."""
+    return registry.spec(env_id)["obs_type"] if env_id is not None else overrides.get("obs_type", "Partial")
+
+
 class VecEnv(object):
     """Batched env: reset() -> obs [N, A, stack, 1, 13, 13] f32 (device);
     step([a_tracker [N], a_target [N]]) -> (obs, rewards [N, A] f32, done [N] uint8, info)."""
 
     def __init__(self, env_id, num_envs, device="cuda:0", seed=1, stack_frames=1, env_id_base=0, auto_reset=None,
-                 rescale=False, obs_u8=False, async_gen=None, inv=False, traces=False, **overrides):
+                 rescale=False, obs_u8=False, async_gen=None, inv=False, traces=False, occlusion=False, **overrides):
         # traces: keep the per-env position record on the device (include/track2d_trace.h: reset() / step() add one small launch)
         # so that render() and info['traces'] exist. It needs the gym protocol (auto_reset=False): with the in-launch auto-reset
         # a terminal step has already replaced the episode's last state.
@@ -59,6 +64,11 @@ class VecEnv(object):
             auto_reset = not self.traces
         if self.traces and auto_reset:
             raise ValueError("traces=True needs auto_reset=False (a finished env's last cell is gone after an in-launch auto-reset)")
+        # occlusion: every cell of both players' windows whose line of sight from the window's centre is blocked by a wall reads
+        # as "unseen" (include/atr_occlusion.h: one more launch behind reset() / step() / observe(), on the raw window, in place)
+        self.occlusion = bool(occlusion)
+        if self.occlusion and _obs_type(env_id, overrides) == "Full":
+            raise ValueError("occlusion=True needs the 13 x 13 windows of a 'Partial' id, %r observes the whole map" % (env_id,))
         self.env_id = env_id
         self.num_envs = num_envs
         self.stack_frames = int(stack_frames)
@@ -130,13 +140,20 @@ class VecEnv(object):
             self._frames = nxt
         return self._frames
 
+    def _occlude(self, obs):
+        """The raw windows [N, 2, 13, 13] as the players see them: occluded in place, on the stream the core's launch went to."""
+        if self.occlusion:
+            from . import occlusion
+            occlusion.occlude_(obs)
+        return obs
+
     def reset(self):
         obs = self.core.reset()
         if self.traces:
             self.core.trace_begin()
         if self.obs_u8:
             obs = obs.to(torch.uint8)        # values 0/1/2/4: exact
-        return self._stack(obs, fill=True)
+        return self._stack(self._occlude(obs), fill=True)
 
     def step(self, actions, out=None):
         """out: optional (obs [N,A,h,w] f32 (u8 with obs_u8), rew [N,A] f32, done [N] u8) device tensors the kernel
@@ -146,7 +163,7 @@ class VecEnv(object):
         obs, rew, done = (self.core.step_u8 if self.obs_u8 else self.core.step)(a0, a1, out=out)
         if self.traces:
             self.core.trace_append(done)
-        return self._stack(obs, done), rew, done, {}
+        return self._stack(self._occlude(obs), done), rew, done, {}
 
     def observe(self):
         """The current observation in reset()'s shape, without stepping (t2d_observe): the frame stack as it stands, the
@@ -154,7 +171,7 @@ class VecEnv(object):
         obs = self.core.observe()
         if self.obs_u8:
             obs = obs.to(torch.uint8)
-        return self._stack(obs, peek=True)
+        return self._stack(self._occlude(obs), peek=True)
 
     # -- snapshots (include/track2d_state.h) ------------------------------------------------------------------
     def _env_mask(self, mask):
@@ -194,8 +211,9 @@ class VecEnv(object):
 
     def fused_step_out(self, out):
         """(core, obs, rew, done) for fused.act_env_step — the env step inside the policy step's last launch — when this
-        env can take it ('Partial' observations, no Nav/RPF target, no host-side frame processing), else None."""
-        if not self.core.supports_u8 or self.stack_frames != 1 or self.rescale:
+        env can take it ('Partial' observations, no Nav/RPF target, no host-side frame processing, no occlusion: its pass
+        follows the env step in a launch of its own), else None."""
+        if not self.core.supports_u8 or self.stack_frames != 1 or self.rescale or self.occlusion:
             return None
         obs, rew, done = out
         if obs.dtype != (torch.uint8 if self.obs_u8 else torch.float32):
@@ -371,7 +389,8 @@ class Track2DEnv(object):
     argument-less np.random.seed() calls inside generators.py:41,56 are NOT replayed (they make the reference itself
     irreproducible; the golden vectors were captured with them neutralised)."""
 
-    def __init__(self, env_id, device="cuda:0", seed=1, stack_frames=1, rescale=False, rng="philox", inv=False, traces=False):
+    def __init__(self, env_id, device="cuda:0", seed=1, stack_frames=1, rescale=False, rng="philox", inv=False, traces=False,
+                 occlusion=False):
         if rng not in ("philox", "numpy"):
             raise ValueError("rng must be 'philox' or 'numpy'")
         self.rng = rng
@@ -384,7 +403,7 @@ class Track2DEnv(object):
             if self._np.scripted:      # the host drives the target; rewards use w_p = 0 either way (track_1v1.py:147-152)
                 over = dict(target_mode_per_env=np.array([registry.TARGET_CODE["Ext"]], np.uint8))
         self.vec = VecEnv(env_id, 1, device=device, seed=seed, stack_frames=stack_frames, auto_reset=False,
-                          rescale=rescale, inv=inv, traces=traces, **over)
+                          rescale=rescale, inv=inv, traces=traces, occlusion=occlusion, **over)
         self.traces = bool(traces)
         self.observation_space, self.action_space = self.vec.observation_space, self.vec.action_space
 
@@ -403,7 +422,7 @@ class Track2DEnv(object):
         core.inject(maze, pos, goals)                      # also zeroes the step / far counters (Track1v1Env.reset)
         if self.traces:
             core.trace_begin()
-        return self.vec._stack(core.observe(), fill=True)[0].cpu().numpy()
+        return self.vec._stack(self.vec._occlude(core.observe()), fill=True)[0].cpu().numpy()
 
     def step(self, action):
         a = [int(np.asarray(x).reshape(-1)[0]) for x in list(action)[:2]]
@@ -477,9 +496,15 @@ def create_env(env_id, args, num_envs=None, device=None, env_id_base=0, obs_u8=N
     rng = rng if rng is not None else getattr(args, "rng", "philox")
     # --render: the env keeps episode traces (and runs without the in-launch auto-reset); a training env passes traces=False
     traces = bool(getattr(args, "render", False)) if traces is None else bool(traces)
+    # --occlusion: walls hide what is behind them, in both players' windows (include/atr_occlusion.h)
+    occlusion = bool(getattr(args, "occlusion", False))
+    if occlusion and registry.spec(env_id)["obs_type"] == "Full":
+        raise ValueError("--occlusion needs the 13 x 13 windows of a 'Partial' id, %r observes the whole map" % (env_id,))
     if n > 1 and rng in ("numpy", "numpy-device"):      # the reference-exact mode for a batch: env i on np.random.seed(seed + env_id_base + i)
         if traces:
             raise NotImplementedError("episode traces / --render are not wired to the batched rng='numpy' envs")
+        if occlusion:
+            raise NotImplementedError("--occlusion is not wired to the batched rng='numpy' envs")
         if stack != 1 or rescale:
             raise NotImplementedError("rng='numpy' with num_envs > 1 returns raw float32 observations (no frame stack / rescale)")
         # rng="numpy-device" / args.np_device: the streams on the device (t2d_np_attach) where the target mode allows it
@@ -487,5 +512,6 @@ def create_env(env_id, args, num_envs=None, device=None, env_id_base=0, obs_u8=N
         return NumpyVecEnv(env_id, [int(seed) + int(env_id_base) + i for i in range(n)], device=device, device_generators=on_dev)
     if n > 1:
         return VecEnv(env_id, n, device=device, seed=seed, stack_frames=stack, env_id_base=env_id_base, rescale=rescale,
-                      obs_u8=obs_u8, inv=inv, traces=traces)
-    return Track2DEnv(env_id, device=device, seed=seed, stack_frames=stack, rescale=rescale, rng=rng, inv=inv, traces=traces)
+                      obs_u8=obs_u8, inv=inv, traces=traces, occlusion=occlusion)
+    return Track2DEnv(env_id, device=device, seed=seed, stack_frames=stack, rescale=rescale, rng=rng, inv=inv, traces=traces,
+                      occlusion=occlusion)

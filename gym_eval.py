@@ -58,6 +58,9 @@ parser.add_argument('--fused-gru', dest='fused_gru', action='store_true',
 parser.add_argument('--full-stem', dest='full_stem', action='store_true',
                     help="whole-map ('Full') ids: the encoders' two convolutions through the HIP stem for 81 / 82 wide frames "
                          'instead of F.conv2d (also ATR_FULL_STEM=1)')
+parser.add_argument('--occlusion', dest='occlusion', action='store_true',
+                    help='walls hide what is behind them: in both players\' 13 x 13 windows every cell whose line of sight from '
+                         'the centre is blocked by a wall reads 5 ("unseen"); --graphed-eval falls back to the eager evaluator')
 
 if __name__ == '__main__':
     args = parser.parse_args()

@@ -130,6 +130,10 @@ parser.add_argument('--sight-stats', dest='sight_stats', action='store_true',
                          'long the shortest way round inside its window is, and how often sight is lost to a wall or to range and '
                          'regained (one more launch per rollout); every --log-every record writes the train/sight_* scalars and '
                          'heatmaps/occlusion_<steps>.png + .npz under --log-dir')
+parser.add_argument('--occlusion', dest='occlusion', action='store_true',
+                    help='walls hide what is behind them: in both players\' 13 x 13 windows every cell whose line of sight from '
+                         'the centre is blocked by a wall reads 5 ("unseen"), in training and in the evaluation rounds (one more '
+                         'launch per env step, and the env step runs outside the policy step\'s last launch)')
 parser.add_argument('--save-shard-state', dest='save_shard_state', action='store_true',
                     help='write the env shard and the players\' recurrent rows to <log-dir>/shard-<rank>.pt after every evaluation '
                          'round and at exit (env snapshot blob of include/track2d_state.h, hxs, cxs, episode lengths, done flags, '
