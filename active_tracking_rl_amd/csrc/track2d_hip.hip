@@ -22,6 +22,7 @@
 #include "../../include/atr_gru_step.h"
 #include "../../include/atr_policy.h"
 #include "../../include/track2d.h"
+#include "../../include/track2d_bank.h"
 #include "../../include/track2d_np.h"
 #include "atr_cell.h"
 #include "coop_gemm.h"
@@ -242,6 +243,23 @@ __device__ __forceinline__ void grow_maze(const DevState &s, uint32_t genv, uint
     gen_maze(tile, lane, ms, r, mlog);
 }
 
+// Map banks (include/track2d_bank.h): K caller-supplied tiles in HBM, [count][kTileWords], followed by one spawn word per map
+// (tracker r | c << 8 | target r << 16 | c << 24, kBankNoSpawn = "sample as usual"). Handed to the generator kernels by value
+// beside DevState (launch_gen), so that no step kernel's arguments change; tiles == nullptr: no bank.
+struct MapBankArg {
+    const uint32_t *tiles;
+    uint32_t count, select;
+};
+constexpr uint32_t kBankNoSpawn = 0xffffffffu;
+// The selection rule of include/track2d_bank.h (wave-uniform arguments).
+__device__ __forceinline__ uint32_t bank_index(const DevState &s, const MapBankArg &b, uint32_t genv, uint32_t episode)
+{
+    if (b.select == (uint32_t)T2D_BANK_CYCLE) return (uint32_t)(((unsigned long long)genv + episode) % b.count);
+    Stream ms;
+    ms.init(s.k0, s.k1, episode, genv, STREAM_MAP, 0);
+    return ms.bounded(b.count - 1u);
+}
+
 // Track1v1Env.reset -> init_maze (track_1v1.py:134-168,218-240) for one env and one episode number, executed by
 // one wave on an LDS tile. All arguments are wave-uniform. `gdir` receives the Nav direction planes.
 // DEFER_NAV: stop before the Nav target's plans (the caller makes them: k_gen_nav spreads the three floods over three waves);
@@ -250,7 +268,8 @@ template <bool NAV, bool DEFER_NAV = false>
 __device__ __forceinline__ void generate_episode(const DevState &s, int e, uint32_t *tile, uint32_t *mlog, int lane, uint32_t cfg,
                                                  uint32_t episode, uint32_t *gdir, uint32_t &pos, uint32_t &goals,
                                                  uint32_t &plan, uint32_t &tctr, uint32_t &navgoal, uint32_t &d2,
-                                                 uint32_t &nav2, FreeIndex &fi_out, uint32_t *stamps = nullptr)
+                                                 uint32_t &nav2, FreeIndex &fi_out, const MapBankArg &bank,
+                                                 uint32_t *stamps = nullptr)
 {
     // T2D_EXP == 9 (probe build only, tools/gen_timeline_probe.py): s_memtime stamps of the generator's phases
 #define T2D_GSTAMP(i) do { if (T2D_EXP == 9 && lane == 0) stamps[i] = (uint32_t)__builtin_readcyclecounter(); } while (0)
@@ -261,7 +280,13 @@ __device__ __forceinline__ void generate_episode(const DevState &s, int e, uint3
     VStream ms;
     ms.init(s.k0, s.k1, episode, genv, STREAM_MAP, 0, lane);
     const int side = side_of_cfg(cfg);
-    if (map_type == MAP_MAZE) {
+    uint32_t fixed = kBankNoSpawn;      // the bank map's spawn word
+    if (bank.tiles) {                   // a banked handle: the tile is fetched, not generated (spare words 0, as the generators leave them)
+        const uint32_t bi = uni(bank_index(s, bank, genv, episode));
+        reinterpret_cast<uint4 *>(tile)[lane] = reinterpret_cast<const uint4 *>(bank.tiles + (size_t)bi * kTileWords)[lane];
+        fixed = uni(bank.tiles[(size_t)bank.count * kTileWords + bi]);
+        wave_lds_sync();
+    } else if (map_type == MAP_MAZE) {
         bool pooled = false;
         if (s.g_maps) {      // grown ahead of time by k_pregrow? (the tag is published after the tile: acquire it)
             const size_t po = (size_t)(episode & 3u) * s.n + e;
@@ -300,21 +325,27 @@ __device__ __forceinline__ void generate_episode(const DevState &s, int e, uint3
     if (rpf) g0 = g1 = rpf_cell(side, 1);
     else sample_goal2();
     // sample_close_states(2, 1), generators.py:53-77 + get_around :82-94 (2x2 block up-left of the tracker)
-    const uint32_t tr = rpf ? rpf_cell(side, 0) : select_free(tile, side, fi, (int)ss.bounded((uint32_t)(n - 1)), lane);
+    const bool fix = fixed != kBankNoSpawn;     // a bank map with a spawn row: no tracker draw, no get_around draw
+    const uint32_t tr = rpf ? rpf_cell(side, 0)
+                            : (fix ? (fixed & 0xffffu) : select_free(tile, side, fi, (int)ss.bounded((uint32_t)(n - 1)), lane));
     const int r = (int)(tr & 0xffu), c = (int)(tr >> 8);
     const int x0 = max(0, r - 1), x1 = min(side - 1, r + 1), y0 = max(0, c - 1), y1 = min(side - 1, c + 1);
     auto gen_free = [&](int rr, int cc) { return tile_bit(tile, rr, cc) == 0u || (rpf && rr == r && cc == c); };
-    int m = 0;
-    for (int rr = x0; rr < x1; rr++)
-        for (int cc = y0; cc < y1; cc++) m += (int)gen_free(rr, cc);
-    int j = (int)ss.bounded((uint32_t)(m - 1));
     uint32_t tg = tr;
-    for (int rr = x0; rr < x1; rr++)
-        for (int cc = y0; cc < y1; cc++)
-            if (gen_free(rr, cc)) {
-                if (j == 0) tg = (uint32_t)rr | ((uint32_t)cc << 8);
-                j--;
-            }
+    if (fix) {
+        tg = fixed >> 16;
+    } else {
+        int m = 0;
+        for (int rr = x0; rr < x1; rr++)
+            for (int cc = y0; cc < y1; cc++) m += (int)gen_free(rr, cc);
+        int j = (int)ss.bounded((uint32_t)(m - 1));
+        for (int rr = x0; rr < x1; rr++)
+            for (int cc = y0; cc < y1; cc++)
+                if (gen_free(rr, cc)) {
+                    if (j == 0) tg = (uint32_t)rr | ((uint32_t)cc << 8);
+                    j--;
+                }
+    }
     while (!rpf && (tr == g0 || tr == g1)) sample_goal2(); // goal_test loop, track_1v1.py:239-240
     pos = tr | (tg << 16);
     goals = g0 | (g1 << 16);
@@ -385,7 +416,7 @@ __device__ __forceinline__ void store_slot_map(const DevState &s, size_t so, con
 // only after the window's join (t2d_handle::gen_*): it may therefore run on the library's side stream, under the
 // step launches and policy kernels of the next window.
 template <bool NAV, bool PREFETCH>
-__global__ __launch_bounds__(256) void k_gen(DevState s, uint32_t lo, uint32_t hi, int force)
+__global__ __launch_bounds__(256) void k_gen(DevState s, uint32_t lo, uint32_t hi, int force, MapBankArg bank)
 {
     __shared__ __attribute__((aligned(16))) uint32_t tiles[kWavesPerBlock][kTileWords];
     __shared__ uint32_t mlogs[kWavesPerBlock][kMazeLogMax];     // move log of the maze generator (t2d_device.h gen_maze)
@@ -414,12 +445,12 @@ __global__ __launch_bounds__(256) void k_gen(DevState s, uint32_t lo, uint32_t h
     __shared__ uint32_t gst[kWavesPerBlock][8];
     if (lane == 0) gst[wave][6] = (uint32_t)__builtin_readcyclecounter();            // kernel entry of this wave (incl. prefetch)
     FreeIndex fi_unused;
-    generate_episode<NAV>(s, e, tile, mlogs[wave], lane, cfg, target, gdir, pos, goals, plan, tctr, navgoal, d2, nav2, fi_unused, gst[wave]);
+    generate_episode<NAV>(s, e, tile, mlogs[wave], lane, cfg, target, gdir, pos, goals, plan, tctr, navgoal, d2, nav2, fi_unused, bank, gst[wave]);
     wave_lds_sync();
     if (lane == 0) { gst[wave][5] = (uint32_t)__builtin_readcyclecounter(); for (int i = 0; i < 7; i++) tile[246 + i] = gst[wave][i]; }
 #else
     FreeIndex fi_unused;
-    generate_episode<NAV>(s, e, tile, mlogs[wave], lane, cfg, target, gdir, pos, goals, plan, tctr, navgoal, d2, nav2, fi_unused);
+    generate_episode<NAV>(s, e, tile, mlogs[wave], lane, cfg, target, gdir, pos, goals, plan, tctr, navgoal, d2, nav2, fi_unused, bank);
 #endif
     wave_lds_sync();
     store_slot_map(s, so, tile, lane, cfg, pos);
@@ -441,7 +472,7 @@ __global__ __launch_bounds__(256) void k_gen(DevState s, uint32_t lo, uint32_t h
 // chain exactly as k_gen does — the results are the oracle's either way, bit for bit (same draws in the same order).
 // PREFETCH: further blocks top up the plan queues of the running episodes, one wave per env (nav_prefetch), as in k_gen.
 template <bool PREFETCH>
-__global__ __launch_bounds__(256) void k_gen_nav(DevState s, uint32_t lo, uint32_t hi, int force)
+__global__ __launch_bounds__(256) void k_gen_nav(DevState s, uint32_t lo, uint32_t hi, int force, MapBankArg bank)
 {
     __shared__ __attribute__((aligned(16))) uint32_t tiles[kWavesPerBlock][kTileWords];
     __shared__ uint32_t mlog[kMazeLogMax];
@@ -469,7 +500,7 @@ __global__ __launch_bounds__(256) void k_gen_nav(DevState s, uint32_t lo, uint32
     FreeIndex fi;
     if (mode != TGT_NAV) {        // other targets of a mixed handle (and RPF): one wave, the whole episode, as k_gen
         if (wave != 0) return;
-        generate_episode<true>(s, e, tile, mlog, lane, cfg, target, gdir, pos, goals, plan, tctr, navgoal, d2, nav2, fi);
+        generate_episode<true>(s, e, tile, mlog, lane, cfg, target, gdir, pos, goals, plan, tctr, navgoal, d2, nav2, fi, bank);
         wave_lds_sync();
         store_slot_map(s, so, tile, lane, cfg, pos);
         if (lane == 0) {
@@ -488,7 +519,7 @@ __global__ __launch_bounds__(256) void k_gen_nav(DevState s, uint32_t lo, uint32
 #endif
     T2D_NSTAMP(6);
     if (wave == 0) {
-        generate_episode<true, true>(s, e, tile, mlog, lane, cfg, target, gdir, pos, goals, plan, tctr, navgoal, d2, nav2, fi, gst);
+        generate_episode<true, true>(s, e, tile, mlog, lane, cfg, target, gdir, pos, goals, plan, tctr, navgoal, d2, nav2, fi, bank, gst);
         // the goals of the two queued plans, drawn as nav_fill_queue will draw them if the first plan needs no re-draw
         Stream t1;
         t1.init(s.k0, s.k1, target, genv, STREAM_TARGET, tctr);
@@ -2344,6 +2375,14 @@ __global__ void k_reward_table(const uint32_t *d2, int n, double w_p, float *r_t
     r_track[i] = (float)a; r_target[i] = (float)b;
 }
 
+// t2d_map_bank_index: the bank index of every env's running episode, one thread per env.
+__global__ __launch_bounds__(256) void k_bank_index(DevState s, MapBankArg bank, int32_t *out)
+{
+    const int e = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (e >= s.n) return;
+    out[e] = (int32_t)bank_index(s, bank, s.env_base + (uint32_t)e, s.episode[e]);
+}
+
 } // namespace t2d
 
 // =====================================================================================================
@@ -2391,6 +2430,8 @@ struct t2d_handle {
     // episode-trace store of csrc/render_hip.hip (t2d_trace_attach): owned here, freed by t2d_destroy through trace_free
     void *trace = nullptr;
     void (*trace_free)(void *) = nullptr;
+    // map bank (t2d_map_bank_attach): the generator kernels' extra argument; the buffer behind bank.tiles is owned here
+    MapBankArg bank = {nullptr, 0u, 0u};
 };
 constexpr int kCoopCtlSets = 4, kCoopCtlWords = 8 * 16;
 
@@ -2562,6 +2603,7 @@ extern "C" int t2d_destroy(t2d_handle *h)
         if (p) (void)hipFree(p);
     if (h->coop_ctl) (void)hipFree(h->coop_ctl);
     if (h->np_act) (void)hipFree(h->np_act);
+    if (h->bank.tiles) (void)hipFree((void *)h->bank.tiles);
     if (h->trace && h->trace_free) h->trace_free(h->trace);
     for (void *p : {(void *)s.g_maps, (void *)s.g_ep, (void *)s.pg_stats, (void *)s.np_mt, (void *)s.np_nav})
         if (p) (void)hipFree(p);
@@ -2624,13 +2666,13 @@ static void launch_gen(t2d_handle *h, hipStream_t st, uint32_t lo, uint32_t hi, 
     // (8192 envs: 927 against 784 us per pass): those keep k_gen.
     if (h->has_navmode && h->s.n <= kGenNavMaxEnvs) {
         const unsigned blocks = 2u * (unsigned)h->s.n + (prefetch ? (unsigned)((h->s.n + kWavesPerBlock - 1) / kWavesPerBlock) : 0u);
-        if (prefetch) hipLaunchKernelGGL((k_gen_nav<true>), dim3(blocks), dim3(256), 0, st, h->s, lo, hi, force);
-        else hipLaunchKernelGGL((k_gen_nav<false>), dim3(blocks), dim3(256), 0, st, h->s, lo, hi, force);
+        if (prefetch) hipLaunchKernelGGL((k_gen_nav<true>), dim3(blocks), dim3(256), 0, st, h->s, lo, hi, force, h->bank);
+        else hipLaunchKernelGGL((k_gen_nav<false>), dim3(blocks), dim3(256), 0, st, h->s, lo, hi, force, h->bank);
         return;
     }
-    if (h->has_nav && prefetch) hipLaunchKernelGGL((k_gen<true, true>), env_grid(3 * h->s.n), dim3(256), 0, st, h->s, lo, hi, force);
-    else if (h->has_nav) hipLaunchKernelGGL((k_gen<true, false>), grid, dim3(256), 0, st, h->s, lo, hi, force);
-    else hipLaunchKernelGGL((k_gen<false, false>), grid, dim3(256), 0, st, h->s, lo, hi, force);
+    if (h->has_nav && prefetch) hipLaunchKernelGGL((k_gen<true, true>), env_grid(3 * h->s.n), dim3(256), 0, st, h->s, lo, hi, force, h->bank);
+    else if (h->has_nav) hipLaunchKernelGGL((k_gen<true, false>), grid, dim3(256), 0, st, h->s, lo, hi, force, h->bank);
+    else hipLaunchKernelGGL((k_gen<false, false>), grid, dim3(256), 0, st, h->s, lo, hi, force, h->bank);
 }
 
 // Make `st` wait for every forked generator launch.
@@ -2653,6 +2695,7 @@ static int join_generator(t2d_handle *h, hipStream_t st)
 static int launch_pregrow(t2d_handle *h, hipStream_t st, int fork)
 {
     if (!h->s.g_maps || h->s.np_mt) return T2D_OK;      // (numpy-stream handles build their maps from the stream, in the pass)
+    if (h->bank.tiles) return T2D_OK;                   // (a banked handle grows no maze)
     const dim3 grid = env_grid(2 * h->s.n);
     if (!fork) {
         hipLaunchKernelGGL(k_pregrow, grid, dim3(256), 0, st, h->s);
@@ -2845,6 +2888,7 @@ extern "C" int t2d_np_attach(t2d_handle *h, const uint32_t *states_host)
 {
     if (!h || !states_host) return fail(T2D_ERR_INVALID, "t2d_np_attach: null argument");
     if (h->primed || h->reset_done) return fail(T2D_ERR_STATE, "t2d_np_attach: attach the streams before the first t2d_reset");
+    if (h->bank.tiles) return fail(T2D_ERR_INVALID, "t2d_np_attach: the handle has a map bank (t2d_map_bank_attach)");
     if ((h->has_ram || h->has_navmode || h->has_rpfmode) && h->s.auto_reset)
         return fail(T2D_ERR_INVALID, "t2d_np_attach: a Ram / Nav / RPF target draws from the stream between resets, so its next episode "
                                      "cannot be generated ahead of the in-launch auto-reset: create the handle with auto_reset = 0 "
@@ -3370,6 +3414,14 @@ static int check_range(const t2d_handle *h, int first, int count, const char *wh
     return T2D_OK;
 }
 
+// One host map (u8 side x side, non-zero = wall) as a bit-packed tile (zeroed by the caller).
+static void pack_tile(const uint8_t *m, int side, uint32_t *t)
+{
+    for (int r = 0; r < side; r++)
+        for (int c = 0; c < side; c++)
+            if (m[r * side + c]) t[r * kRowWords + (c >> 5)] |= 1u << (c & 31);
+}
+
 extern "C" int t2d_inject(t2d_handle *h, int first, int count, int side, const uint8_t *maze_host,
                           const int32_t *pos_host, const int32_t *goals_host, void *stream)
 {
@@ -3386,10 +3438,7 @@ extern "C" int t2d_inject(t2d_handle *h, int first, int count, int side, const u
         cnt((size_t)count), zero((size_t)count, 0u), d2((size_t)count), navgoal((size_t)count);
     for (int i = 0; i < count; i++) {
         const uint8_t *m = maze_host + (size_t)i * side * side;
-        uint32_t *t = tiles.data() + (size_t)i * kTileWords;
-        for (int r = 0; r < side; r++)
-            for (int c = 0; c < side; c++)
-                if (m[r * side + c]) t[r * kRowWords + (c >> 5)] |= 1u << (c & 31);
+        pack_tile(m, side, tiles.data() + (size_t)i * kTileWords);
         const int32_t *p = pos_host + (size_t)i * 4;
         for (int k = 0; k < 4; k++)
             if (p[k] < 0 || p[k] >= side) return fail(T2D_ERR_INVALID, "t2d_inject: position outside the map (env %d)", first + i);
@@ -3427,6 +3476,97 @@ extern "C" int t2d_inject(t2d_handle *h, int first, int count, int side, const u
     if (h->n_has_episode == s.n) h->reset_done = true;      // (all at once or env by env)
     return T2D_OK;
 }
+
+// ---- map banks (include/track2d_bank.h) ------------------------------------------------------------------------------------
+// Validate `count` host maps and spawn rows and pack them: tiles [count][kTileWords], then one spawn word per map. Pure host
+// code. Returns 0, or -1 with the map and the reason in `why`.
+static int bank_pack(const uint8_t *maps, const int32_t *spawns, int count, int side, std::vector<uint32_t> &out, char *why,
+                     size_t why_len)
+{
+    out.assign((size_t)count * kTileWords + (size_t)count, 0u);
+    for (int i = 0; i < count; i++) {
+        const uint8_t *m = maps + (size_t)i * side * side;
+        int n_free = 0;
+        for (int r = 0; r < side; r++)
+            for (int c = 0; c < side; c++) {
+                const uint8_t v = m[r * side + c];
+                if (v > 1) { snprintf(why, why_len, "map %d: cell (%d, %d) is %u, not 0 / 1", i, r, c, v); return -1; }
+                if (!v && (r == 0 || c == 0 || r == side - 1 || c == side - 1)) {
+                    snprintf(why, why_len, "map %d: border cell (%d, %d) is not a wall", i, r, c);
+                    return -1;
+                }
+                n_free += v == 0;
+            }
+        if (n_free < 3) { snprintf(why, why_len, "map %d: %d free cell(s), at least 3 are needed", i, n_free); return -1; }
+        pack_tile(m, side, out.data() + (size_t)i * kTileWords);
+        uint32_t word = kBankNoSpawn;
+        if (spawns) {
+            const int32_t *p = spawns + (size_t)i * 4;
+            if (!(p[0] == -1 && p[1] == -1 && p[2] == -1 && p[3] == -1)) {
+                for (int k = 0; k < 4; k++)
+                    if (p[k] < 0 || p[k] >= side) {
+                        snprintf(why, why_len, "map %d: spawn row (%d, %d, %d, %d) is neither all -1 nor inside the map", i, p[0], p[1], p[2], p[3]);
+                        return -1;
+                    }
+                if (m[p[0] * side + p[1]] || m[p[2] * side + p[3]]) {
+                    snprintf(why, why_len, "map %d: spawn row (%d, %d, %d, %d) places an agent on a wall", i, p[0], p[1], p[2], p[3]);
+                    return -1;
+                }
+                word = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+            }
+        }
+        out[(size_t)count * kTileWords + (size_t)i] = word;
+    }
+    return 0;
+}
+
+extern "C" int t2d_map_bank_attach(t2d_handle *h, const uint8_t *maps_host, const int32_t *spawns_host, int count, int side,
+                                   int select, void *stream)
+{
+    if (!h || !maps_host) return fail(T2D_ERR_INVALID, "t2d_map_bank_attach: null handle or maps");
+    if (h->bank.tiles) return fail(T2D_ERR_STATE, "t2d_map_bank_attach: the handle already has a map bank");
+    if (h->primed || h->reset_done || h->n_has_episode > 0)
+        return fail(T2D_ERR_STATE, "t2d_map_bank_attach: attach the bank before the first t2d_reset / t2d_inject");
+    if (count < 1 || count > T2D_BANK_MAX_MAPS)
+        return fail(T2D_ERR_INVALID, "t2d_map_bank_attach: count %d outside 1 .. %d", count, T2D_BANK_MAX_MAPS);
+    if (select != T2D_BANK_CYCLE && select != T2D_BANK_RANDOM) return fail(T2D_ERR_INVALID, "t2d_map_bank_attach: select %d", select);
+    if (h->s.np_mt) return fail(T2D_ERR_INVALID, "t2d_map_bank_attach: the handle draws from numpy streams (t2d_np_attach)");
+    if (h->has_rpf) return fail(T2D_ERR_INVALID, "t2d_map_bank_attach: the handle has T2D_TGT_RPF / T2D_TGT_EXT envs");
+    // (obs_side is 81 exactly when every env is a Maze env; a handle that mixes Maze with Block / Empty has no one side)
+    if ((h->has_maze && h->s.obs_side != 81) || side != h->s.obs_side)
+        return fail(T2D_ERR_INVALID, "t2d_map_bank_attach: side %d, but %s", side,
+                    h->has_maze && h->s.obs_side != 81 ? "the handle mixes sides 81 (Maze) and 82"
+                                                       : (h->s.obs_side == 81 ? "the handle's envs have side 81 (Maze)"
+                                                                              : "the handle's envs have side 82 (Block / Empty)"));
+    std::vector<uint32_t> packed;
+    char why[256];
+    if (bank_pack(maps_host, spawns_host, count, side, packed, why, sizeof(why))) return fail(T2D_ERR_INVALID, "t2d_map_bank_attach: %s", why);
+    DeviceGuard guard(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    uint32_t *buf = nullptr;
+    HIP_TRY(hipMalloc((void **)&buf, packed.size() * sizeof(uint32_t)));
+    hipError_t err = hipMemcpyAsync(buf, packed.data(), packed.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st);
+    if (err == hipSuccess) err = hipStreamSynchronize(st);
+    if (err != hipSuccess) {
+        (void)hipFree(buf);
+        return fail(T2D_ERR_HIP, "t2d_map_bank_attach: copy failed: %s", hipGetErrorString(err));
+    }
+    h->bank.tiles = buf; h->bank.count = (uint32_t)count; h->bank.select = (uint32_t)select;
+    return T2D_OK;
+}
+
+extern "C" int t2d_map_bank_index(t2d_handle *h, int32_t *idx_dev, void *stream)
+{
+    if (!h || !idx_dev) return fail(T2D_ERR_INVALID, "t2d_map_bank_index: null argument");
+    if (!h->bank.tiles) return fail(T2D_ERR_STATE, "t2d_map_bank_index: no map bank attached (t2d_map_bank_attach)");
+    if (!h->primed) return fail(T2D_ERR_STATE, "t2d_map_bank_index: call t2d_reset first");
+    DeviceGuard guard(h->device);
+    hipLaunchKernelGGL(k_bank_index, dim3((unsigned)((h->s.n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, h->s, h->bank, idx_dev);
+    HIP_TRY(hipGetLastError());
+    return T2D_OK;
+}
+
+extern "C" int t2d_map_bank_count(const t2d_handle *h) { return h && h->bank.tiles ? (int)h->bank.count : 0; }
 
 extern "C" int t2d_inject_plan(t2d_handle *h, int env, const int32_t *plan_host, int len, int cursor, void *stream)
 {

@@ -55,7 +55,8 @@ class VecEnv(object):
     step([a_tracker [N], a_target [N]]) -> (obs, rewards [N, A] f32, done [N] uint8, info)."""
 
     def __init__(self, env_id, num_envs, device="cuda:0", seed=1, stack_frames=1, env_id_base=0, auto_reset=None,
-                 rescale=False, obs_u8=False, async_gen=None, inv=False, traces=False, occlusion=False, **overrides):
+                 rescale=False, obs_u8=False, async_gen=None, inv=False, traces=False, occlusion=False, map_bank=None,
+                 bank_select="random", **overrides):
         # traces: keep the per-env position record on the device (include/track2d_trace.h: reset() / step() add one small launch)
         # so that render() and info['traces'] exist. It needs the gym protocol (auto_reset=False): with the in-launch auto-reset
         # a terminal step has already replaced the episode's last state.
@@ -97,6 +98,11 @@ class VecEnv(object):
             for box in self.observation_space:
                 box.low, box.high = -1.0, 1.0
         self.device = self.core.device
+        # map_bank: every episode's map comes from the bank (include/track2d_bank.h). Attached here, before any reset and so
+        # before any graph capture: captured generator launches hold the bank argument by value.
+        self.map_bank = None
+        if map_bank is not None:
+            self.map_bank = self.core.attach_map_bank(map_bank, bank_select)
         self._frames = None
         self._seed = seed
         if self.traces:
@@ -239,6 +245,10 @@ class VecEnv(object):
                             dtype=torch.uint8 if self.obs_u8 else torch.float32),
                 torch.empty((num_steps, self.num_envs, 2), dtype=torch.float32, device=dev),
                 torch.empty((num_steps, self.num_envs), dtype=torch.uint8, device=dev))
+
+    def map_index(self, out=None):
+        """int32 [N] (device): the bank index of every env's current episode (VecTrack2D.map_index); needs a map bank."""
+        return self.core.map_index(out)
 
     def flush(self):
         self.core.flush()
@@ -390,7 +400,7 @@ class Track2DEnv(object):
     irreproducible; the golden vectors were captured with them neutralised)."""
 
     def __init__(self, env_id, device="cuda:0", seed=1, stack_frames=1, rescale=False, rng="philox", inv=False, traces=False,
-                 occlusion=False):
+                 occlusion=False, map_bank=None, bank_select="random"):
         if rng not in ("philox", "numpy"):
             raise ValueError("rng must be 'philox' or 'numpy'")
         self.rng = rng
@@ -400,10 +410,13 @@ class Track2DEnv(object):
             from .np_mode import NpEpisodeSource
             sp = registry.spec(env_id)
             self._np = NpEpisodeSource(sp["map_type"], sp["target_mode"], sp["level"], seed)
+            if map_bank is not None:
+                raise NotImplementedError("a map bank replaces the device generators; rng='numpy' builds its maps on the host")
             if self._np.scripted:      # the host drives the target; rewards use w_p = 0 either way (track_1v1.py:147-152)
                 over = dict(target_mode_per_env=np.array([registry.TARGET_CODE["Ext"]], np.uint8))
         self.vec = VecEnv(env_id, 1, device=device, seed=seed, stack_frames=stack_frames, auto_reset=False,
-                          rescale=rescale, inv=inv, traces=traces, occlusion=occlusion, **over)
+                          rescale=rescale, inv=inv, traces=traces, occlusion=occlusion, map_bank=map_bank,
+                          bank_select=bank_select, **over)
         self.traces = bool(traces)
         self.observation_space, self.action_space = self.vec.observation_space, self.vec.action_space
 
@@ -468,6 +481,18 @@ class Track2DEnv(object):
         return self.vec.render(mode=mode, env=0, scale=scale, trace=trace)
 
 
+def eval_args(args):
+    """The flags an EVALUATION shard is created with: args itself, unless it names a map bank — then a copy whose map_bank is
+    --eval-map-bank's file (none: generated maps, whatever the training envs run on), served in 'cycle' order so that every
+    round meets the same maps."""
+    if getattr(args, "map_bank", None) is None and getattr(args, "eval_map_bank", None) is None:
+        return args
+    import copy
+    a = copy.copy(args)
+    a.map_bank, a.bank_select = getattr(args, "eval_map_bank", None), "cycle"
+    return a
+
+
 def create_env(env_id, args, num_envs=None, device=None, env_id_base=0, obs_u8=None, rng=None, traces=None):
     """environment.create_env (environment.py:11-32) for the Track2D ids.
 
@@ -500,6 +525,11 @@ def create_env(env_id, args, num_envs=None, device=None, env_id_base=0, obs_u8=N
     occlusion = bool(getattr(args, "occlusion", False))
     if occlusion and registry.spec(env_id)["obs_type"] == "Full":
         raise ValueError("--occlusion needs the 13 x 13 windows of a 'Partial' id, %r observes the whole map" % (env_id,))
+    # --map-bank FILE / --bank-select: the envs run on the file's maps (include/track2d_bank.h)
+    bank = getattr(args, "map_bank", None) or None
+    select = getattr(args, "bank_select", None) or "random"
+    if bank is not None and rng in ("numpy", "numpy-device"):
+        raise NotImplementedError("--map-bank replaces the device generators; rng='numpy' builds its maps from numpy's stream")
     if n > 1 and rng in ("numpy", "numpy-device"):      # the reference-exact mode for a batch: env i on np.random.seed(seed + env_id_base + i)
         if traces:
             raise NotImplementedError("episode traces / --render are not wired to the batched rng='numpy' envs")
@@ -512,6 +542,6 @@ def create_env(env_id, args, num_envs=None, device=None, env_id_base=0, obs_u8=N
         return NumpyVecEnv(env_id, [int(seed) + int(env_id_base) + i for i in range(n)], device=device, device_generators=on_dev)
     if n > 1:
         return VecEnv(env_id, n, device=device, seed=seed, stack_frames=stack, env_id_base=env_id_base, rescale=rescale,
-                      obs_u8=obs_u8, inv=inv, traces=traces, occlusion=occlusion)
+                      obs_u8=obs_u8, inv=inv, traces=traces, occlusion=occlusion, map_bank=bank, bank_select=select)
     return Track2DEnv(env_id, device=device, seed=seed, stack_frames=stack, rescale=rescale, rng=rng, inv=inv, traces=traces,
-                      occlusion=occlusion)
+                      occlusion=occlusion, map_bank=bank, bank_select=select)

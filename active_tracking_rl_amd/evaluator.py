@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import fused, vec_env
-from .environment import create_env
+from .environment import create_env, eval_args
 from .player_util import Agent
 from .train import _GraphedSchedule, rollout
 
@@ -154,9 +154,10 @@ class GreedyEvaluator(_GraphedSchedule):
         self._alive_host = torch.empty(n, dtype=torch.uint8).pin_memory()
         self.sampler = fused.ActionSampler(self.device, seed=0)      # (the greedy step draws nothing: it only carries ordinals)
         self.stats, self.record = {}, None
+        self.map_index = None            # with --eval-map-bank: int32 [episodes], each evaluation episode's bank index
 
     def _make_env(self):
-        return create_env(self.env_id, self.args, num_envs=max(2, self.episodes), device=str(self.device),
+        return create_env(self.env_id, eval_args(self.args), num_envs=max(2, self.episodes), device=str(self.device),
                           env_id_base=getattr(self.args, "eval_env_id_base", 1 << 20), obs_u8=True)
 
     def _player(self, env, accounts):
@@ -201,6 +202,8 @@ class GreedyEvaluator(_GraphedSchedule):
             self._warm_up()
             t1 = time.perf_counter()
             player = self.master = self._player(self.env, (self.rsum, self.length, self.alive))
+            if getattr(self.env, "map_bank", None) is not None:
+                self.map_index = self.env.map_index()[:self.episodes].cpu().numpy()
             self._new_carry()
             if self.keep:
                 first_obs = player.state.reshape(player.num_envs, 2, 13, 13).clone()

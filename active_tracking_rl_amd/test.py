@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import registry
-from .environment import create_env
+from .environment import create_env, eval_args
 from .model import build_model
 from .player_util import Agent
 from .utils import ScalarWriter, check_path, setup_logger, write_png
@@ -75,7 +75,7 @@ def heuristic_players(model, env_id, heuristic_tracker=None, heuristic_target=No
 
 @torch.no_grad()
 def evaluate(model, env_id, args, device, episodes, seed=None, graphed=False, render_dir=None, heuristic_tracker=None,
-             heuristic_target=None):
+             heuristic_target=None, info=None):
     """Run `episodes` envs of `env_id` in parallel until each has finished ONE episode. Returns per-episode reward
     sums [episodes, 2] and lengths [episodes] (numpy). graphed: the round on the rollout's kernels as replayed hipGraphs
     (evaluator.GreedyEvaluator) where they apply, else — with one warning line — the eager round below.
@@ -84,7 +84,9 @@ def evaluate(model, env_id, args, device, episodes, seed=None, graphed=False, re
     numbers are those of a round without rendering. (A finished env of such a shard is simply stepped on from where it stands —
     the step kernels treat it like any other env — while its trace stays closed: no masked reset is needed.)
     heuristic_tracker='pursuit' / heuristic_target='evade': that player's actions come from the heuristic player
-    (heuristic_players: the round is the eager one; model may be None when no model action reaches the env)."""
+    (heuristic_players: the round is the eager one; model may be None when no model action reaches the env).
+    info: a dict that receives what the round knows beyond its return value — with --eval-map-bank, info['map_index']: int32
+    [episodes], the bank index of each evaluation episode's map (map_index() right after the reset)."""
     global _warned_heuristic_graphed
     heuristic = heuristic_players(model, env_id, heuristic_tracker, heuristic_target)
     if graphed and heuristic != (None, None):
@@ -99,10 +101,14 @@ def evaluate(model, env_id, args, device, episodes, seed=None, graphed=False, re
     if graphed:
         from . import evaluator
         try:
-            return evaluator.GreedyEvaluator(model, env_id, args, device, episodes).run()
+            gev = evaluator.GreedyEvaluator(model, env_id, args, device, episodes)
+            out = gev.run()
+            if info is not None and gev.map_index is not None:
+                info["map_index"] = gev.map_index
+            return out
         except evaluator.Unsupported as ex:
             logging.getLogger(__name__).warning("graphed evaluation falls back to the eager round: %s", ex)
-    ev = create_env(env_id, args, num_envs=max(2, episodes), device=str(device),
+    ev = create_env(env_id, eval_args(args), num_envs=max(2, episodes), device=str(device),
                     env_id_base=getattr(args, "eval_env_id_base", 1 << 20), traces=render_dir is not None)
     n = ev.num_envs
     was_training = model is not None and model.training
@@ -111,6 +117,8 @@ def evaluate(model, env_id, args, device, episodes, seed=None, graphed=False, re
     player = Agent(model, ev, args, None, device)
     player.heuristic = heuristic
     player.reset()
+    if info is not None and getattr(ev, "map_bank", None) is not None:
+        info["map_index"] = ev.map_index()[:episodes].cpu().numpy()
     rsum = torch.zeros(n, player.num_agents, device=device)
     length = torch.zeros(n, dtype=torch.int32, device=device)
     alive = torch.ones(n, dtype=torch.bool, device=device)
@@ -180,6 +188,30 @@ def save_checkpoints(model, args, n_iter, best):
     return model_dir
 
 
+PER_MAP_LOG_MAX = 64        # --eval-map-bank: banks of at most this many maps get per-map scalars
+
+
+def per_map_summary(map_index, rsum, length):
+    """The evaluation episodes of a round grouped by bank index: a list of dict(map, episodes, eps_len, success_rate, reward)
+    in index order — mean length, share of episodes that lasted the 500 steps, mean returns per player."""
+    map_index, rsum, length = np.asarray(map_index), np.asarray(rsum), np.asarray(length)
+    rows = []
+    for m in np.unique(map_index):
+        sel = map_index == m
+        rows.append(dict(map=int(m), episodes=int(sel.sum()), eps_len=float(length[sel].mean()),
+                         success_rate=float((length[sel] >= registry.MAX_EPISODE_STEPS).mean()), reward=rsum[sel].mean(0)))
+    return rows
+
+
+def log_per_map(writer, map_index, rsum, length, n_iter, count=None):
+    """test/map/<idx>/eps_len and test/map/<idx>/reward0: the round's means per bank map (banks of at most PER_MAP_LOG_MAX maps)."""
+    if map_index is None or (count if count is not None else int(np.max(map_index)) + 1) > PER_MAP_LOG_MAX:
+        return
+    for row in per_map_summary(map_index, rsum, length):
+        writer.add_scalar('test/map/{0}/eps_len'.format(row["map"]), row["eps_len"], n_iter)
+        writer.add_scalar('test/map/{0}/reward0'.format(row["map"]), row["reward"][0], n_iter)
+
+
 def heuristic_rounds(args, model, device, writer, log, n_iter, state):
     """--eval-heuristic: two more rounds of --test-eps episodes on args.env after an evaluation round — the model's tracker
     against the evading target (test/vs_evade/reward0, test/vs_evade/eps_len) and the model's target against the pursuit tracker
@@ -227,8 +259,9 @@ def test(args, shared_model, train_modes, n_iters, rounds=None, state=None):
         t0 = time.time()
         n_iter = int(sum(n_iters))
         render_dir = os.path.join(args.log_dir, 'render', 'iter{0}'.format(n_iter)) if getattr(args, "render", False) else None
+        info = {}
         rsum, length = evaluate(shared_model, env_id, args, device, args.test_eps,
-                                graphed=bool(getattr(args, "graphed_eval", False)), render_dir=render_dir)
+                                graphed=bool(getattr(args, "graphed_eval", False)), render_dir=render_dir, info=info)
         schedule_train_modes(args, train_modes, n_iter, state)                       # test.py:84-92
         # test.py:93-97: one record per evaluation episode at step n_iter. test/fps in the reference is the env steps per
         # second of the evaluator's one env; here the episodes of a round run as one batch, so it is the round's env steps
@@ -239,6 +272,7 @@ def test(args, shared_model, train_modes, n_iters, rounds=None, state=None):
                 writer.add_scalar('test/reward' + str(i), rsum[ep, i], n_iter)
             writer.add_scalar('test/fps', fps, n_iter)
             writer.add_scalar('test/eps_len', length[ep], n_iter)
+        log_per_map(writer, info.get("map_index"), rsum, length, n_iter)
         writer.flush()
         ave_reward_sum = rsum[:, :2].sum(0) / args.test_eps
         len_mean = length.sum() / args.test_eps

@@ -337,6 +337,10 @@ class VecTrack2D(object):
         cfg.action_type = 1 if action_type == "Moore" else 0
         self.action_type, self.num_actions = action_type, 8 if action_type == "Moore" else 4
         self.obs_type = obs_type
+        # the side of every env's map: 81 when all are Maze envs, else 82 (a handle that mixes the two has no one side)
+        self.map_side = 81 if ((map_type == "Maze") if map_type_per_env is None
+                               else bool((np.asarray(map_type_per_env) == 1).all())) else 82
+        self.map_bank, self.bank_select = None, None
         if obs_type == "Full":   # track_1v1.py:254-256: Box(shape=(1, S, S)); S = 81 for Maze maps, else 82
             all_maze = (map_type == "Maze") if map_type_per_env is None else bool((np.asarray(map_type_per_env) == 1).all())
             self.obs_hw = (81, 81) if all_maze else (82, 82)
@@ -487,6 +491,34 @@ class VecTrack2D(object):
     def snapshot(self):
         """A new EnvSnapshot of this env (contents undefined until its first save() or load_bytes())."""
         return EnvSnapshot(self)
+
+    # -- map banks (include/track2d_bank.h) ----------------------------------------------------------------------
+    def attach_map_bank(self, bank, select="cycle"):
+        """Before the first reset: every episode this handle generates takes its map from `bank` (a map_bank.MapBank, a bank
+        file's name or a [K, S, S] array; smaller maps are padded with walls to the handle's side) instead of from the
+        generators. select: 'cycle' ((global env id + episode) mod K) or 'random' (one draw of the episode's MAP stream)."""
+        from . import map_bank
+        code = map_bank.select_code(select)
+        bank = map_bank.as_bank(bank).fit(self.map_side)
+        sp = None if bank.spawns is None else _np_ptr(bank.spawns)
+        map_bank.lib().t2d_map_bank_attach(self.h, _np_ptr(bank.maps), sp, bank.count, bank.side, code, self._stream())
+        self.map_bank, self.bank_select = bank, select
+        return bank
+
+    @property
+    def map_bank_count(self):
+        """K of the attached bank, 0 without one."""
+        from . import map_bank
+        return int(map_bank.lib().t2d_map_bank_count(self.h))
+
+    def map_index(self, out=None):
+        """int32 [N] on the device: the bank index of every env's current episode. One launch on the current stream, no
+        synchronisation (capturable)."""
+        from . import map_bank
+        idx = out if out is not None else torch.empty((self.num_envs,), dtype=torch.int32, device=self.device)
+        assert idx.is_cuda and idx.dtype == torch.int32 and idx.is_contiguous() and idx.numel() == self.num_envs
+        map_bank.lib().t2d_map_bank_index(self.h, C.c_void_p(idx.data_ptr()), self._stream())
+        return idx
 
     # -- heuristic players (include/track2d_heuristic.h) -------------------------------------------------------
     def heuristic_actions(self, roles=("pursuit", "evade"), out=None, dist=None):

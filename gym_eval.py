@@ -15,7 +15,7 @@ import torch
 from active_tracking_rl_amd import build
 from active_tracking_rl_amd.environment import _spaces
 from active_tracking_rl_amd.model import build_model
-from active_tracking_rl_amd.test import evaluate
+from active_tracking_rl_amd.test import evaluate, per_map_summary
 from active_tracking_rl_amd import registry
 from active_tracking_rl_amd.utils import check_path, setup_logger
 
@@ -58,6 +58,9 @@ parser.add_argument('--fused-gru', dest='fused_gru', action='store_true',
 parser.add_argument('--full-stem', dest='full_stem', action='store_true',
                     help="whole-map ('Full') ids: the encoders' two convolutions through the HIP stem for 81 / 82 wide frames "
                          'instead of F.conv2d (also ATR_FULL_STEM=1)')
+parser.add_argument('--map-bank', default=None, metavar='FILE',
+                    help='evaluate on the maps of a bank file (.npz / .txt: python -m active_tracking_rl_amd.map_bank), episode e '
+                         'on map (eval env id of e + 1) mod K; --csv then also writes <csv>.maps.csv, one row per map')
 parser.add_argument('--occlusion', dest='occlusion', action='store_true',
                     help='walls hide what is behind them: in both players\' 13 x 13 windows every cell whose line of sight from '
                          'the centre is blocked by a wall reads 5 ("unseen"); --graphed-eval falls back to the eager evaluator')
@@ -89,8 +92,10 @@ if __name__ == '__main__':
         model.player1.load_state_dict(load(args.load_target))             # :88-92
     args.gpu_ids = [device.index]
     render_dir = (args.render_dir or os.path.join(args.log_dir, 'render')) if args.render else None
+    args.eval_map_bank, args.map_bank = args.map_bank, None        # (the evaluation shard's flag: environment.eval_args)
+    info = {}
     rsum, length = evaluate(model, args.env, args, device, args.num_episodes, graphed=args.graphed_eval, render_dir=render_dir,
-                            heuristic_tracker=args.heuristic_tracker, heuristic_target=args.heuristic_target)
+                            heuristic_tracker=args.heuristic_tracker, heuristic_target=args.heuristic_target, info=info)
     reward_mean, reward_std = rsum.mean(0), rsum.std(0)
     len_mean, len_std = length.mean(), length.std()
     success_rate = float((length >= 500).mean())
@@ -107,3 +112,10 @@ if __name__ == '__main__':
             if new:
                 w.writeheader()
             w.writerows([row])
+        if info.get("map_index") is not None:          # --map-bank: the same figures per map, beside the summary
+            root = args.csv[:-4] if args.csv.endswith('.csv') else args.csv
+            with open(root + '.maps.csv', 'w') as f:
+                w = csv.writer(f)
+                w.writerow(['Map', 'Episodes', 'EL_mean', 'S_rate', 'R0_mean', 'R1_mean'])
+                for r in per_map_summary(info["map_index"], rsum, length):
+                    w.writerow([r["map"], r["episodes"], r["eps_len"], r["success_rate"], float(r["reward"][0]), float(r["reward"][1])])

@@ -134,6 +134,14 @@ parser.add_argument('--occlusion', dest='occlusion', action='store_true',
                     help='walls hide what is behind them: in both players\' 13 x 13 windows every cell whose line of sight from '
                          'the centre is blocked by a wall reads 5 ("unseen"), in training and in the evaluation rounds (one more '
                          'launch per env step, and the env step runs outside the policy step\'s last launch)')
+parser.add_argument('--map-bank', default=None, metavar='FILE',
+                    help='train on the maps of a bank file (.npz / .txt: python -m active_tracking_rl_amd.map_bank) instead of '
+                         'generated ones: every episode of every env, the in-launch auto-reset included, takes its map from the bank')
+parser.add_argument('--bank-select', default='random', choices=('random', 'cycle'),
+                    help='--map-bank: which map an episode gets: one draw of its own random stream, or (env + episode) mod K')
+parser.add_argument('--eval-map-bank', default=None, metavar='FILE',
+                    help='run the evaluation rounds (--env-base) on the maps of this bank file, in cycle order; with at most 64 '
+                         'maps every round also writes test/map/<idx>/eps_len and test/map/<idx>/reward0')
 parser.add_argument('--save-shard-state', dest='save_shard_state', action='store_true',
                     help='write the env shard and the players\' recurrent rows to <log-dir>/shard-<rank>.pt after every evaluation '
                          'round and at exit (env snapshot blob of include/track2d_state.h, hxs, cxs, episode lengths, done flags, '
