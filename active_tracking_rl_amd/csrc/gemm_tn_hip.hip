@@ -2,7 +2,9 @@
 // M, N in {128 .. 1024}): the weight-gradient GEMMs of the learner (dW_fc = dpre^T x, dW_ih = dG^T feat,
 // dW_hh = h^T dG). The library kernels TunableOp picks run these long-K / small-output shapes at 74-110 TFLOP/s (28 for the
 // M = 128 case as a plain mm); this kernel is built for exactly this shape class on the f32 matrix cores (96-101
-// TFLOP/s on all of them, 2.5% of an A3C iteration saved; also tighter error than the library's split-K order):
+// TFLOP/s on all of them, 2.5% of an A3C iteration saved; also tighter error than the library's split-K order on the products:
+// 0.18-0.29 of its error against float64 per output tile; the column sums are on a par with the library's, 0.6-1.8 of its error,
+// tests/test_gemm_tn_f64_gpu.py):
 //   * 128 x 128 output tile per workgroup (4 waves, each a 64 x 64 quadrant = 2 x 2 v_mfma_f32_32x32x2_f32 tiles,
 //     64 accumulator VGPRs), the K range split over many workgroups (split-K) so that ~512 workgroups exist;
 //   * both operands are consumed in their natural row-major layout: a 16- or 32-row chunk of X1 and of X2 (by K: tn_kc) is staged in LDS
@@ -364,6 +366,8 @@ static int group_tiles(const atr_gemm_tn_problem *pr, int count)
     for (int q = 0; q < count; q++) {
         if (!pr[q].x1 || !pr[q].x2 || !pr[q].c || pr[q].M <= 0 || pr[q].N <= 0 || pr[q].M % kTile || pr[q].N % kTile) return -1;
         if ((pr[q].ld1 && (pr[q].ld1 < pr[q].M || pr[q].ld1 % 4)) || (pr[q].ld2 && (pr[q].ld2 < pr[q].N || pr[q].ld2 % 4))) return -1;
+        // x1 / x2 are read as float4 and by 16-byte global_load_lds, c is written as float4 (row_scale: scalar reads, any address)
+        if (((uintptr_t)pr[q].x1 | (uintptr_t)pr[q].x2 | (uintptr_t)pr[q].c | (uintptr_t)pr[q].colsum0 | (uintptr_t)pr[q].colsum1) % 16) return -1;
         tiles += (pr[q].M / kTile) * (pr[q].N / kTile);
     }
     return tiles;
@@ -456,7 +460,7 @@ extern "C" int atr_gemm_tn_set_corun(int on)
 extern "C" long long atr_gemm_tn_workspace_floats(long long K, int M, int N)
 {
     atr_gemm_tn_problem p = {};
-    float dummy = 0.f;
+    alignas(16) float dummy = 0.f;           // (a stand-in that passes group_tiles' alignment check)
     p.x1 = p.x2 = &dummy; p.c = &dummy; p.M = M; p.N = N; p.colsum0 = &dummy;
     return atr_gemm_tn_grouped_workspace_floats(&p, 1, K);
 }

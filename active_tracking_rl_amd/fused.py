@@ -1834,6 +1834,7 @@ class DeferredWeightGrads(object):
                         and x2.stride(1) == 1 and x2.stride(0) >= N and x2.stride(0) % 4 == 0
                         and x2.data_ptr() % 16 == 0)
                 or tuple(dst.shape) != (M, N) or any(tuple(v.shape) != (M,) for v in bv)
+                or any(v.data_ptr() % 16 for v in [dst] + bv)
                 or (row_scale is not None and not row_scale.is_contiguous())):
             return None
         return (x1, x2, dst, row_scale, int(shift), bv, M, N), (whole, bw)
@@ -1937,13 +1938,14 @@ class gemm_tn_corun(object):
 @torch.no_grad()
 def gemm_tn(x1, x2, row_scale=None, colsum=False):
     """x1.t() @ x2 for tall row-major x1 [K,M], x2 [K,N] — the weight-gradient GEMMs (csrc/gemm_tn_hip.hip) when the
-    shape fits the kernel (CUDA fp32, contiguous, M and N multiples of 128), otherwise the library GEMM.
+    shape fits the kernel (CUDA fp32, contiguous, 16-byte aligned, M and N multiples of 128), otherwise the library GEMM.
     row_scale [K]: x1's rows are multiplied by it first; colsum=True: also return (scaled x1).sum(0) — the bias
     gradient that goes with the weight gradient — from the same pass."""
     K, M = x1.shape
     N = x2.shape[1]
     if (use_gemm_tn and x1.is_cuda and x1.dtype == torch.float32 and x2.dtype == torch.float32 and M % 128 == 0
-            and N % 128 == 0 and K >= 4096 and x1.is_contiguous() and x2.is_contiguous()):
+            and N % 128 == 0 and K >= 4096 and x1.is_contiguous() and x2.is_contiguous()
+            and x1.data_ptr() % 16 == 0 and x2.data_ptr() % 16 == 0):       # (the kernel reads both 16 bytes at a time)
         L = lib()
         ws = torch.empty(L.atr_gemm_tn_workspace_floats(K, M, N), dtype=torch.float32, device=x1.device)
         c = torch.empty((M, N), dtype=torch.float32, device=x1.device)

@@ -424,6 +424,7 @@ typedef struct atr_gemm_tn_problem {
     float *colsum0, *colsum1;
     int M, N;
     long long ld1, ld2;      /* row strides of x1 / x2 in floats (0 = dense: M / N); multiples of 4 */
+    /* x1, x2, c, colsum0 and colsum1 must be 16-byte aligned (refused otherwise); row_scale may start at any float */
 } atr_gemm_tn_problem;
 long long atr_gemm_tn_grouped_workspace_floats(const atr_gemm_tn_problem *problems, int count, long long K);
 /* Co-run mode of the weight-gradient kernel, a setting of the CALLING THREAD, returns the previous setting: while on, launches (and the workspace
