@@ -26,7 +26,7 @@ HEADERS = ["t2d_device.h", os.path.join("..", "..", "include", "track2d.h"),
            os.path.join("..", "..", "include", "track2d_state.h"), "t2d_state_view.h",
            os.path.join("..", "..", "include", "atr_stem_full.h"), os.path.join("..", "..", "include", "track2d_heuristic.h"),
            os.path.join("..", "..", "include", "atr_sight.h"), os.path.join("..", "..", "include", "atr_occlusion.h"),
-           os.path.join("..", "..", "include", "track2d_bank.h")]
+           os.path.join("..", "..", "include", "track2d_bank.h"), os.path.join("..", "..", "include", "track2d_bank_prio.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wno-unused-result"]
 LDFLAGS = ["--offload-arch=gfx950", "-fPIC", "-shared", "-ldl"]

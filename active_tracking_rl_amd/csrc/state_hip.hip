@@ -172,6 +172,7 @@ struct t2d_snapshot {
     SnapIdent id;
     uint32_t random_step;
     bool valid;                         // a full save or an import has filled every row
+    bool prio;                          // the owner was a prioritised handle when the snapshot was created (refused from then on)
     uint32_t *arr[kStateArrays];
     long long payload;                  // bytes
 };
@@ -216,6 +217,7 @@ extern "C" int t2d_snapshot_create(t2d_handle *h, t2d_snapshot **out)
     t2d_snapshot *s = new (std::nothrow) t2d_snapshot();
     if (!s) return refuse(T2D_ERR_INVALID, "t2d_snapshot_create: out of host memory");
     s->owner = h; s->device = v.device; s->random_step = 0; s->valid = false; s->payload = 0;
+    s->prio = v.prio_enabled != 0;
     for (uint32_t *&p : s->arr) p = nullptr;
     s->id.n = (uint32_t)v.n; s->id.env_base = v.env_base; s->id.seed = (uint64_t)v.k0 | ((uint64_t)v.k1 << 32);
     s->id.max_steps = v.max_steps; s->id.auto_reset = v.auto_reset;
@@ -261,6 +263,11 @@ static int open_pair(t2d_handle *h, const t2d_snapshot *s, const char *who, t2d_
     int rc = open_handle(h, who, v);
     if (rc) return rc;
     if (s->owner != h) return refuse(T2D_ERR_INVALID, "%s: the snapshot was created for another handle", who);
+    // prioritized map replay (include/track2d_bank_prio.h): an episode's bank index is what the table drew when the slot was
+    // generated, kept in a ring beside the table and the accounts, none of which a snapshot holds
+    if (v.prio_enabled)
+        return refuse(T2D_ERR_STATE, "%s: the handle draws its maps from a priority table (t2d_bank_prio_enable): the index ring, "
+                                     "the table and the accounts are not part of a snapshot, so the handle cannot be rewound", who);
     if (!v.ready) return refuse(T2D_ERR_STATE, "%s: call t2d_reset (all envs) first", who);
     return T2D_OK;
 }
@@ -324,6 +331,9 @@ extern "C" int t2d_snapshot_export(const t2d_snapshot *s, void *blob_host, long 
 extern "C" int t2d_snapshot_import(t2d_snapshot *s, const void *blob_host, long long bytes, void *stream)
 {
     if (!s || !blob_host) return refuse(T2D_ERR_INVALID, "t2d_snapshot_import: null argument");
+    if (s->prio)
+        return refuse(T2D_ERR_STATE, "t2d_snapshot_import: the snapshot belongs to a handle that draws its maps from a priority table "
+                                     "(t2d_bank_prio_enable): the index ring, the table and the accounts are not part of a snapshot");
     if (bytes < (long long)T2D_SNAPSHOT_HEADER_BYTES)
         return refuse(T2D_ERR_INVALID, "t2d_snapshot_import: size %lld is shorter than the %d-byte header", bytes, T2D_SNAPSHOT_HEADER_BYTES);
     const uint8_t *b = static_cast<const uint8_t *>(blob_host);

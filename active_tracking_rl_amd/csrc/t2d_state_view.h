@@ -31,6 +31,7 @@ struct t2d_state_view {
     int ready;                  // every env has a current episode and, with auto_reset, valid next slots
     int np_attached;            // t2d_np_attach was called
     int trace_attached;         // t2d_trace_attach was called
+    int prio_enabled;           // t2d_bank_prio_enable was called (the index ring and the table are not part of a snapshot)
     const uint32_t *cfg;        // [N] per-env configuration words (device)
     uint32_t *random_step;      // the handle's t2d_step_random counter (host)
     uint32_t *arr[t2d::kStateArrays];   // device arrays in kStateArray order

@@ -23,6 +23,7 @@
 #include "../../include/atr_policy.h"
 #include "../../include/track2d.h"
 #include "../../include/track2d_bank.h"
+#include "../../include/track2d_bank_prio.h"
 #include "../../include/track2d_np.h"
 #include "atr_cell.h"
 #include "coop_gemm.h"
@@ -246,9 +247,13 @@ __device__ __forceinline__ void grow_maze(const DevState &s, uint32_t genv, uint
 // Map banks (include/track2d_bank.h): K caller-supplied tiles in HBM, [count][kTileWords], followed by one spawn word per map
 // (tracker r | c << 8 | target r << 16 | c << 24, kBankNoSpawn = "sample as usual"). Handed to the generator kernels by value
 // beside DevState (launch_gen), so that no step kernel's arguments change; tiles == nullptr: no bank.
+// Prioritized map replay (include/track2d_bank_prio.h, t2d_bank_prio_enable): cum != nullptr — the index is drawn from the
+// table cum[count] and remembered in the ring chosen[T2D_PRIO_RING][N]; `select` is then ignored.
 struct MapBankArg {
     const uint32_t *tiles;
     uint32_t count, select;
+    const uint32_t *cum;
+    int32_t *chosen;
 };
 constexpr uint32_t kBankNoSpawn = 0xffffffffu;
 // The selection rule of include/track2d_bank.h (wave-uniform arguments).
@@ -258,6 +263,33 @@ __device__ __forceinline__ uint32_t bank_index(const DevState &s, const MapBankA
     Stream ms;
     ms.init(s.k0, s.k1, episode, genv, STREAM_MAP, 0);
     return ms.bounded(b.count - 1u);
+}
+
+// The weighted draw of include/track2d_bank_prio.h, by one whole wave (wave-uniform arguments, all 64 lanes active):
+// r = bounded(cum[K - 1] - 1) of the episode's MAP stream, idx = #{i : cum[i] <= r}. cum is non-decreasing, so the predicate
+// is a prefix of the table and the count is found by a 64-ary search: each round every lane probes one of 64 evenly spaced
+// entries of the open range [lo, hi) and a ballot counts the probes that hold — 65536 -> 1024 -> 16 -> 1 entries, three
+// rounds of one load each instead of 17 dependent ones. Every probe index is below hi <= K.
+__device__ __forceinline__ uint32_t prio_draw(const DevState &s, const MapBankArg &b, uint32_t genv, uint32_t episode, int lane)
+{
+    const uint32_t K = b.count;
+    if (K == 1u) return 0u;
+    const uint32_t total = uni(b.cum[K - 1u]);
+    Stream ms;
+    ms.init(s.k0, s.k1, episode, genv, STREAM_MAP, 0);
+    const uint32_t r = uni(ms.bounded(total - 1u));
+    uint32_t lo = 0u, hi = K;               // every i < lo holds (cum[i] <= r), no i >= hi does
+    while (lo < hi) {
+        const uint32_t step = (hi - lo + 63u) >> 6;
+        const uint32_t p = lo + ((uint32_t)lane + 1u) * step - 1u;
+        const bool holds = p < hi && b.cum[p] <= r;
+        const uint32_t c = (uint32_t)__popcll(__ballot(holds));
+        const uint32_t first_fail = lo + (c + 1u) * step - 1u;      // the probe of lane c (if it lies in the range, it failed)
+        lo = lo + c * step;
+        hi = c < 64u && first_fail < hi ? first_fail : hi;
+        lo = lo < hi ? lo : hi;
+    }
+    return lo < K ? lo : K - 1u;            // (r < cum[K - 1]: the count is below K)
 }
 
 // Track1v1Env.reset -> init_maze (track_1v1.py:134-168,218-240) for one env and one episode number, executed by
@@ -282,7 +314,13 @@ __device__ __forceinline__ void generate_episode(const DevState &s, int e, uint3
     const int side = side_of_cfg(cfg);
     uint32_t fixed = kBankNoSpawn;      // the bank map's spawn word
     if (bank.tiles) {                   // a banked handle: the tile is fetched, not generated (spare words 0, as the generators leave them)
-        const uint32_t bi = uni(bank_index(s, bank, genv, episode));
+        uint32_t bi;
+        if (bank.cum) {                 // prioritised: the table's draw, remembered for t2d_map_bank_index and the accounts
+            bi = uni(prio_draw(s, bank, genv, episode, lane));
+            if (lane == 0) bank.chosen[(size_t)(episode & (T2D_PRIO_RING - 1)) * s.n + e] = (int32_t)bi;
+        } else {
+            bi = uni(bank_index(s, bank, genv, episode));
+        }
         reinterpret_cast<uint4 *>(tile)[lane] = reinterpret_cast<const uint4 *>(bank.tiles + (size_t)bi * kTileWords)[lane];
         fixed = uni(bank.tiles[(size_t)bank.count * kTileWords + bi]);
         wave_lds_sync();
@@ -2380,7 +2418,138 @@ __global__ __launch_bounds__(256) void k_bank_index(DevState s, MapBankArg bank,
 {
     const int e = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (e >= s.n) return;
-    out[e] = (int32_t)bank_index(s, bank, s.env_base + (uint32_t)e, s.episode[e]);
+    if (bank.cum) out[e] = bank.chosen[(size_t)(s.episode[e] & (T2D_PRIO_RING - 1)) * s.n + e];     // (prioritised: what was drawn)
+    else out[e] = (int32_t)bank_index(s, bank, s.env_base + (uint32_t)e, s.episode[e]);
+}
+
+// ---- prioritized map replay (include/track2d_bank_prio.h) -------------------------------------------------------------------
+constexpr int kPrioBlock = 1024;        // k_prio_set_weights: one workgroup, thread j owns the entries [j * per, (j + 1) * per)
+constexpr int kPrioWaves = kPrioBlock / 64;
+
+__device__ __forceinline__ bool prio_counts(float w) { return w > 0.0f && w <= 3.402823466e+38f; }     // (NaN fails both)
+__device__ __forceinline__ uint32_t prio_quantum(float w, double w_max, double S)
+{
+    if (!prio_counts(w)) return 0u;
+    const double ratio = (double)w / w_max;     // (rounded; -ffp-contract=off and no addition follows: nothing to fuse)
+    const double q = floor(ratio * S);
+    return q < 1.0 ? 1u : (uint32_t)q;
+}
+
+// t2d_bank_prio_set_weights: w[K] -> cum[K]. Three passes of one workgroup over a table of at most 256 KiB: the maximum
+// (lane shuffles, then LDS), every thread's sum of its quanta and the workgroup's exclusive scan of those, the running sums.
+// The quanta are recomputed in the third pass instead of kept: at most 64 per thread, two float64 operations each.
+__global__ __launch_bounds__(kPrioBlock) void k_prio_set_weights(const float *__restrict__ w, uint32_t *__restrict__ cum, int K)
+{
+    __shared__ float s_max[kPrioWaves];
+    __shared__ uint32_t s_sum[kPrioWaves];
+    const int j = (int)threadIdx.x, lane = j & 63, wave = j >> 6;
+    const int per = (K + kPrioBlock - 1) / kPrioBlock, i0 = j * per, i1 = min(K, i0 + per);
+    float m = 0.0f;
+    for (int i = i0; i < i1; i++) {
+        const float v = w[i];
+        if (prio_counts(v)) m = fmaxf(m, v);
+    }
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    if (lane == 0) s_max[wave] = m;
+    __syncthreads();
+    m = s_max[0];
+    for (int k = 1; k < kPrioWaves; k++) m = fmaxf(m, s_max[k]);
+    const double w_max = (double)m, S = (double)(0x7fffffffu / (uint32_t)K);
+    // (m == 0: no weight counts, every quantum below is 0 and the table falls back to uniform)
+    uint32_t sum = 0u;
+    for (int i = i0; i < i1; i++) sum += prio_quantum(w[i], w_max, S);
+    const bool uniform = m == 0.0f;
+    if (uniform) sum = (uint32_t)max(0, i1 - i0);
+    uint32_t incl = sum;                     // inclusive scan over the wave, then over the waves' totals
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t up = __shfl_up(incl, o);
+        if (lane >= o) incl += up;
+    }
+    if (lane == 63) s_sum[wave] = incl;
+    __syncthreads();
+    uint32_t run = incl - sum;
+    for (int k = 0; k < wave; k++) run += s_sum[k];
+    for (int i = i0; i < i1; i++) {
+        run += uniform ? 1u : prio_quantum(w[i], w_max, S);
+        cum[i] = run;
+    }
+}
+
+// t2d_bank_prio_score: one thread per env (the loop of k_episode_stats, csrc/episode_stats_hip.hip, with the episode's map
+// looked up in the ring at every done flag).
+__global__ __launch_bounds__(64) void k_prio_score(DevState s, MapBankArg bank, const float *__restrict__ rew, long long rew_st,
+                                                   long long rew_sn, long long rew_sp, const uint8_t *__restrict__ done,
+                                                   long long done_st, long long done_sn, float *__restrict__ run_ret,
+                                                   int *__restrict__ run_len, unsigned long long *__restrict__ stat, int T,
+                                                   int success_len)
+{
+    const int e = (int)(blockIdx.x * 64 + threadIdx.x);
+    if (e >= s.n) return;
+    const float *re = rew + (long long)e * rew_sn;
+    const uint8_t *de = done + (long long)e * done_sn;
+    uint32_t d = 0u;
+    for (int t = 0; t < T; t++) d += de[t * done_st] ? 1u : 0u;
+    const uint32_t ep_end = s.episode[e];
+    uint32_t ep = ep_end - d;                // the episode running at step 0
+    float r0 = run_ret[2 * e], r1 = run_ret[2 * e + 1];
+    int len = run_len[e];
+    unsigned long long *lost = stat + (size_t)bank.count * T2D_PRIO_FIELDS;
+#pragma unroll 4
+    for (int t = 0; t < T; t++) {
+        const float a0 = re[t * rew_st], a1 = re[t * rew_st + rew_sp];
+        const uint8_t dn = de[t * done_st];
+        r0 = r0 + a0;
+        r1 = r1 + a1;
+        len += 1;
+        if (dn) {
+            const int32_t m = ep_end - ep <= (uint32_t)T2D_PRIO_KEEP ? bank.chosen[(size_t)(ep & (T2D_PRIO_RING - 1)) * s.n + e] : -1;
+            if (m >= 0 && (uint32_t)m < bank.count) {
+                unsigned long long *f = stat + (size_t)m * T2D_PRIO_FIELDS;
+                atomicAdd(f + 0, 1ull);
+                atomicAdd(f + 1, (unsigned long long)len);
+                if (len >= success_len) atomicAdd(f + 2, 1ull);
+                atomicAdd(f + 3, (unsigned long long)llrint((double)r0 * 65536.0));
+                atomicAdd(f + 4, (unsigned long long)llrint((double)r1 * 65536.0));
+            } else {
+                atomicAdd(lost, 1ull);
+            }
+            r0 = 0.0f;
+            r1 = 0.0f;
+            len = 0;
+            ep += 1u;
+        }
+    }
+    run_ret[2 * e] = r0;
+    run_ret[2 * e + 1] = r1;
+    run_len[e] = len;
+}
+
+// t2d_bank_prio_drain: copy out and zero, one element per thread.
+__global__ __launch_bounds__(256) void k_prio_drain(unsigned long long *__restrict__ stat, unsigned long long *__restrict__ out,
+                                                    long long count)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    out[i] = stat[i];
+    stat[i] = 0ull;
+}
+
+// t2d_bank_prio_enable: the uniform table, the empty ring, zeroed accounts and carry, in one launch.
+__global__ __launch_bounds__(256) void k_prio_init(uint32_t *cum, int K, int32_t *chosen, long long ring, unsigned long long *stat,
+                                                   long long stats, float *run_ret, int *run_len, int n)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < K) cum[i] = (uint32_t)i + 1u;
+    if (i < ring) chosen[i] = -1;
+    if (i < stats) stat[i] = 0ull;
+    if (i < n) { run_ret[2 * i] = 0.0f; run_ret[2 * i + 1] = 0.0f; run_len[i] = 0; }
+}
+
+// A t2d_reset of every env of a prioritised handle: the episodes in flight are gone.
+__global__ __launch_bounds__(256) void k_prio_clear_carry(float *run_ret, int *run_len, int n)
+{
+    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (i < n) { run_ret[2 * i] = 0.0f; run_ret[2 * i + 1] = 0.0f; run_len[i] = 0; }
 }
 
 } // namespace t2d
@@ -2431,7 +2600,12 @@ struct t2d_handle {
     void *trace = nullptr;
     void (*trace_free)(void *) = nullptr;
     // map bank (t2d_map_bank_attach): the generator kernels' extra argument; the buffer behind bank.tiles is owned here
-    MapBankArg bank = {nullptr, 0u, 0u};
+    MapBankArg bank = {nullptr, 0u, 0u, nullptr, nullptr};
+    // prioritized map replay (t2d_bank_prio_enable): bank.cum / bank.chosen and these are owned here. prio_stat: [K * 5 + 1]
+    // int64 accounts + the unattributed counter; prio_ret / prio_len: the carry of t2d_bank_prio_score
+    unsigned long long *prio_stat = nullptr;
+    float *prio_ret = nullptr;
+    int *prio_len = nullptr;
 };
 constexpr int kCoopCtlSets = 4, kCoopCtlWords = 8 * 16;
 
@@ -2604,6 +2778,8 @@ extern "C" int t2d_destroy(t2d_handle *h)
     if (h->coop_ctl) (void)hipFree(h->coop_ctl);
     if (h->np_act) (void)hipFree(h->np_act);
     if (h->bank.tiles) (void)hipFree((void *)h->bank.tiles);
+    for (void *p : {(void *)h->bank.cum, (void *)h->bank.chosen, (void *)h->prio_stat, (void *)h->prio_ret, (void *)h->prio_len})
+        if (p) (void)hipFree(p);
     if (h->trace && h->trace_free) h->trace_free(h->trace);
     for (void *p : {(void *)s.g_maps, (void *)s.g_ep, (void *)s.pg_stats, (void *)s.np_mt, (void *)s.np_nav})
         if (p) (void)hipFree(p);
@@ -2637,6 +2813,7 @@ extern "C" int t2d_state_view_get(t2d_handle *h, t2d_state_view *out)
     out->ready = h->reset_done && (h->primed || !s.auto_reset) ? 1 : 0;
     out->np_attached = s.np_mt != nullptr ? 1 : 0;
     out->trace_attached = h->trace != nullptr ? 1 : 0;
+    out->prio_enabled = h->bank.cum != nullptr ? 1 : 0;
     out->cfg = s.cfg; out->random_step = &h->random_step;
     uint32_t *const arrs[kStateArrays] = {
         s.maps, s.pos, s.goals, s.cnt, s.episode, s.plan, s.tctr, s.navgoal, s.nav2, s.d2,
@@ -3044,6 +3221,8 @@ extern "C" int t2d_reset(t2d_handle *h, const uint8_t *mask_dev, float *obs_dev,
     }
     launch_env<OP_RESET, false>(h, st, nullptr, nullptr, 0, mask_dev, obs_dev, nullptr, nullptr, 0u, 0u, 0u, 1u);
     launch_gen(h, st, 1u, 1u, 0); // refill the consumed next slots, in order on the caller's stream
+    if (h->bank.cum && mask_dev == nullptr && h->reset_done)    // (prioritised, every env restarted: t2d_bank_prio_score's carry)
+        hipLaunchKernelGGL(k_prio_clear_carry, dim3((unsigned)((h->s.n + 255) / 256)), dim3(256), 0, st, h->prio_ret, h->prio_len, h->s.n);
     HIP_TRY(hipGetLastError());
     if (mask_dev == nullptr) h->reset_done = true;
     return T2D_OK;
@@ -3567,6 +3746,105 @@ extern "C" int t2d_map_bank_index(t2d_handle *h, int32_t *idx_dev, void *stream)
 }
 
 extern "C" int t2d_map_bank_count(const t2d_handle *h) { return h && h->bank.tiles ? (int)h->bank.count : 0; }
+
+// ---- prioritized map replay (include/track2d_bank_prio.h) -------------------------------------------------------------------
+extern "C" int t2d_bank_prio_enable(t2d_handle *h, void *stream)
+{
+    if (!h) return fail(T2D_ERR_INVALID, "t2d_bank_prio_enable: null handle");
+    if (!h->bank.tiles) return fail(T2D_ERR_STATE, "t2d_bank_prio_enable: no map bank attached (t2d_map_bank_attach)");
+    if (h->bank.cum) return fail(T2D_ERR_STATE, "t2d_bank_prio_enable: the handle already draws from a priority table");
+    if (h->primed || h->reset_done || h->n_has_episode)
+        return fail(T2D_ERR_STATE, "t2d_bank_prio_enable: enable the priorities before the first t2d_reset / t2d_inject");
+    DeviceGuard guard(h->device);
+    const int K = (int)h->bank.count, n = h->s.n;
+    const long long ring = (long long)T2D_PRIO_RING * n, stats = (long long)K * T2D_PRIO_FIELDS + 1;
+    uint32_t *cum = nullptr;
+    int32_t *chosen = nullptr;
+    unsigned long long *stat = nullptr;
+    float *ret = nullptr;
+    int *len = nullptr;
+    hipError_t err = hipMalloc((void **)&cum, (size_t)K * sizeof(uint32_t));
+    if (err == hipSuccess) err = hipMalloc((void **)&chosen, (size_t)ring * sizeof(int32_t));
+    if (err == hipSuccess) err = hipMalloc((void **)&stat, (size_t)stats * sizeof(unsigned long long));
+    if (err == hipSuccess) err = hipMalloc((void **)&ret, (size_t)n * 2 * sizeof(float));
+    if (err == hipSuccess) err = hipMalloc((void **)&len, (size_t)n * sizeof(int));
+    if (err == hipSuccess) {
+        const long long most = std::max(std::max((long long)K, ring), std::max(stats, (long long)n));
+        hipLaunchKernelGGL(k_prio_init, dim3((unsigned)((most + 255) / 256)), dim3(256), 0, (hipStream_t)stream, cum, K, chosen, ring,
+                           stat, stats, ret, len, n);
+        err = hipGetLastError();
+    }
+    if (err == hipSuccess) err = hipStreamSynchronize((hipStream_t)stream);
+    if (err != hipSuccess) {
+        for (void *p : {(void *)cum, (void *)chosen, (void *)stat, (void *)ret, (void *)len})
+            if (p) (void)hipFree(p);
+        return fail(T2D_ERR_HIP, "t2d_bank_prio_enable: allocation or initialisation failed: %s", hipGetErrorString(err));
+    }
+    h->prio_stat = stat; h->prio_ret = ret; h->prio_len = len;
+    h->bank.chosen = chosen; h->bank.cum = cum;
+    return T2D_OK;
+}
+
+extern "C" int t2d_bank_prio_set_weights(t2d_handle *h, const float *w_dev, void *stream)
+{
+    if (!h || !w_dev) return fail(T2D_ERR_INVALID, "t2d_bank_prio_set_weights: null argument");
+    if (!h->bank.cum) return fail(T2D_ERR_STATE, "t2d_bank_prio_set_weights: the handle has no priorities (t2d_bank_prio_enable)");
+    DeviceGuard guard(h->device);
+    int rc = join_generator(h, (hipStream_t)stream);    // (a forked generator pass reads the table: write it behind the pass)
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_prio_set_weights, dim3(1), dim3(kPrioBlock), 0, (hipStream_t)stream, w_dev,
+                       const_cast<uint32_t *>(h->bank.cum), (int)h->bank.count);
+    HIP_TRY(hipGetLastError());
+    return T2D_OK;
+}
+
+extern "C" int t2d_bank_prio_score(t2d_handle *h, const float *rew, long long rew_st, long long rew_sn, long long rew_sp,
+                                   const unsigned char *done, long long done_st, long long done_sn, int T, int success_len,
+                                   void *stream)
+{
+    if (!h || !rew || !done) return fail(T2D_ERR_INVALID, "t2d_bank_prio_score: null argument");
+    if (!h->bank.cum) return fail(T2D_ERR_STATE, "t2d_bank_prio_score: the handle has no priorities (t2d_bank_prio_enable)");
+    if (!h->reset_done) return fail(T2D_ERR_STATE, "t2d_bank_prio_score: call t2d_reset first");
+    if (T < 1) return fail(T2D_ERR_INVALID, "t2d_bank_prio_score: needs T > 0 (T %d)", T);
+    if (rew_st < 0 || rew_sn < 0 || rew_sp < 0 || done_st < 0 || done_sn < 0)
+        return fail(T2D_ERR_INVALID, "t2d_bank_prio_score: negative element stride");
+    if ((uintptr_t)rew & 3u) return fail(T2D_ERR_INVALID, "t2d_bank_prio_score: rew %p is not 4-byte aligned", (const void *)rew);
+    DeviceGuard guard(h->device);
+    hipLaunchKernelGGL(k_prio_score, dim3((unsigned)((h->s.n + 63) / 64)), dim3(64), 0, (hipStream_t)stream, h->s, h->bank, rew, rew_st,
+                       rew_sn, rew_sp, (const uint8_t *)done, done_st, done_sn, h->prio_ret, h->prio_len, h->prio_stat, T, success_len);
+    HIP_TRY(hipGetLastError());
+    return T2D_OK;
+}
+
+// Internal seam (not part of include/track2d_bank_prio.h, like t2d_state_view_get): copies of the table cum [K] u32 and of the
+// ring chosen [8][N] i32 into the caller's device buffers (either may be null), in order on `stream`. What the tests hold the
+// table to bit for bit; nothing else reads it.
+extern "C" int t2d_prio_peek(t2d_handle *h, uint32_t *cum_out_dev, int32_t *chosen_out_dev, void *stream)
+{
+    if (!h) return fail(T2D_ERR_INVALID, "t2d_prio_peek: null handle");
+    if (!h->bank.cum) return fail(T2D_ERR_STATE, "t2d_prio_peek: the handle has no priorities (t2d_bank_prio_enable)");
+    DeviceGuard guard(h->device);
+    if (cum_out_dev)
+        HIP_TRY(hipMemcpyAsync(cum_out_dev, h->bank.cum, (size_t)h->bank.count * sizeof(uint32_t), hipMemcpyDeviceToDevice,
+                               (hipStream_t)stream));
+    if (chosen_out_dev)
+        HIP_TRY(hipMemcpyAsync(chosen_out_dev, h->bank.chosen, (size_t)T2D_PRIO_RING * h->s.n * sizeof(int32_t),
+                               hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return T2D_OK;
+}
+
+extern "C" int t2d_bank_prio_drain(t2d_handle *h, long long *out_dev, void *stream)
+{
+    if (!h || !out_dev) return fail(T2D_ERR_INVALID, "t2d_bank_prio_drain: null argument");
+    if (!h->bank.cum) return fail(T2D_ERR_STATE, "t2d_bank_prio_drain: the handle has no priorities (t2d_bank_prio_enable)");
+    if ((uintptr_t)out_dev & 7u) return fail(T2D_ERR_INVALID, "t2d_bank_prio_drain: out %p is not 8-byte aligned", (void *)out_dev);
+    DeviceGuard guard(h->device);
+    const long long count = (long long)h->bank.count * T2D_PRIO_FIELDS + 1;
+    hipLaunchKernelGGL(k_prio_drain, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, (hipStream_t)stream, h->prio_stat,
+                       (unsigned long long *)out_dev, count);
+    HIP_TRY(hipGetLastError());
+    return T2D_OK;
+}
 
 extern "C" int t2d_inject_plan(t2d_handle *h, int env, const int32_t *plan_host, int len, int cursor, void *stream)
 {

@@ -56,7 +56,7 @@ class VecEnv(object):
 
     def __init__(self, env_id, num_envs, device="cuda:0", seed=1, stack_frames=1, env_id_base=0, auto_reset=None,
                  rescale=False, obs_u8=False, async_gen=None, inv=False, traces=False, occlusion=False, map_bank=None,
-                 bank_select="random", **overrides):
+                 bank_select="random", map_priority=None, map_priority_opts=None, **overrides):
         # traces: keep the per-env position record on the device (include/track2d_trace.h: reset() / step() add one small launch)
         # so that render() and info['traces'] exist. It needs the gym protocol (auto_reset=False): with the in-launch auto-reset
         # a terminal step has already replaced the episode's last state.
@@ -103,6 +103,15 @@ class VecEnv(object):
         self.map_bank = None
         if map_bank is not None:
             self.map_bank = self.core.attach_map_bank(map_bank, bank_select)
+        # map_priority ('tracker' | 'target'): prioritized map replay on the bank (include/track2d_bank_prio.h; map_priority.py).
+        # Enabled right after the attach, for the same reason; map_priority_opts: every, beta, rho, alpha of MapPriority.
+        self.map_priority = None
+        if map_priority is not None:
+            if self.map_bank is None:
+                raise ValueError("map_priority=%r needs a map bank (map_bank=...)" % (map_priority,))
+            from .map_priority import MapPriority
+            self.core.enable_map_priority()
+            MapPriority(self, self.device, map_priority, **(map_priority_opts or {}))       # (attaches itself)
         self._frames = None
         self._seed = seed
         if self.traces:
@@ -490,6 +499,7 @@ def eval_args(args):
     import copy
     a = copy.copy(args)
     a.map_bank, a.bank_select = getattr(args, "eval_map_bank", None), "cycle"
+    a.map_priority = None           # (priorities belong to the training shards: held-out banks stay in cycle order)
     return a
 
 
@@ -530,6 +540,19 @@ def create_env(env_id, args, num_envs=None, device=None, env_id_base=0, obs_u8=N
     select = getattr(args, "bank_select", None) or "random"
     if bank is not None and rng in ("numpy", "numpy-device"):
         raise NotImplementedError("--map-bank replaces the device generators; rng='numpy' builds its maps from numpy's stream")
+    # --map-priority ROLE: prioritized map replay on the bank (include/track2d_bank_prio.h; map_priority.py)
+    prio = getattr(args, "map_priority", None) or None
+    if prio is not None and bank is None:
+        raise ValueError("--map-priority needs --map-bank")
+    if prio is not None and n <= 1:
+        raise NotImplementedError("--map-priority is wired to the batched envs (num_envs > 1)")
+    prio_opts = None
+    if prio is not None:
+        from . import map_priority as mp
+        prio_opts = dict(every=getattr(args, "map_priority_every", None) or mp.EVERY,
+                         beta=getattr(args, "map_priority_beta", None) or mp.BETA,
+                         rho=mp.RHO if getattr(args, "map_priority_rho", None) is None else args.map_priority_rho,
+                         alpha=mp.ALPHA if getattr(args, "map_priority_alpha", None) is None else args.map_priority_alpha)
     if n > 1 and rng in ("numpy", "numpy-device"):      # the reference-exact mode for a batch: env i on np.random.seed(seed + env_id_base + i)
         if traces:
             raise NotImplementedError("episode traces / --render are not wired to the batched rng='numpy' envs")
@@ -542,6 +565,7 @@ def create_env(env_id, args, num_envs=None, device=None, env_id_base=0, obs_u8=N
         return NumpyVecEnv(env_id, [int(seed) + int(env_id_base) + i for i in range(n)], device=device, device_generators=on_dev)
     if n > 1:
         return VecEnv(env_id, n, device=device, seed=seed, stack_frames=stack, env_id_base=env_id_base, rescale=rescale,
-                      obs_u8=obs_u8, inv=inv, traces=traces, occlusion=occlusion, map_bank=bank, bank_select=select)
+                      obs_u8=obs_u8, inv=inv, traces=traces, occlusion=occlusion, map_bank=bank, bank_select=select,
+                      map_priority=prio, map_priority_opts=prio_opts)
     return Track2DEnv(env_id, device=device, seed=seed, stack_frames=stack, rescale=rescale, rng=rng, inv=inv, traces=traces,
                       occlusion=occlusion, map_bank=bank, bank_select=select)

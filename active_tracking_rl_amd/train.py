@@ -119,10 +119,28 @@ def rollout(player, num_steps, fast=True):
         if buf is None or buf[2].shape[0] != num_steps:
             raise RuntimeError("sight statistics read the rollout store, and this rollout has none (fast=%s)" % fast)
         sight.update(buf[0], buf[1], buf[2])
+    # map priorities (map_priority.MapPriority, opt-in, attached to the env shard in the same way; the carry and the per-map
+    # accounts live in the env handle): one launch over the step rewards and done flags, behind the other statistics.
+    prio = getattr(player.env, "map_priority", None)
+    if prio is not None:
+        buf = player._buf if fast else None
+        if buf is not None and buf[2].shape[0] == num_steps:
+            prio.update(buf[1], buf[2])
+        else:
+            prio.update(torch.stack(player.rewards[-num_steps:]), torch.stack(player.dones[-num_steps:]))
     # A rollout that is not a whole number of generator stamp cycles restarts the stamps (so that a captured rollout
     # replays consistently); otherwise forked generator launches stay in flight under the learner's kernels.
     if hasattr(player.env, "flush") and num_steps % getattr(player.env, "generator_cycle", 1) != 0:
         player.env.flush()
+
+
+def tick_map_priority(env, stream=None):
+    """Before a rollout over `env` is issued (eagerly or as a graph replay): the shard's map priorities, where it has any, count
+    the rollout and refresh their table every --map-priority-every-th time — eagerly, between two rollouts, in stream order
+    on the stream the rollouts run on. Nothing attached: nothing is launched."""
+    prio = getattr(env, "map_priority", None)
+    if prio is not None:
+        prio.tick(stream)
 
 
 def capture_allreduce_default():
@@ -342,6 +360,7 @@ class GraphedIteration(_GraphedSchedule):
         g = self.g_rolls.get(mode)
         if g is None:
             g = self._capture(mode)
+        tick_map_priority(self.player.env)
         g.replay()
         if not self.capture_allreduce:
             self.player.allreduce_grads(self.optimizer)
@@ -594,6 +613,7 @@ class PipelinedIteration(_GraphedSchedule):
             # the same graphs in program order on the caller's stream: R(i), L(i), O(i). The one-update delay lives in the
             # double-buffered weights (rollout i + 1 reads F_{1-k}, which O(i) does not touch), not in the timing, so this
             # is the same dataflow as the two-stream schedule below
+            tick_map_priority(self.players[k].env)
             g_r.replay()
             g_l.replay()
             if not self.capture_allreduce:
@@ -611,6 +631,7 @@ class PipelinedIteration(_GraphedSchedule):
             with torch.cuda.stream(self.sR):
                 if self.i >= 2:
                     self.sR.wait_event(self.ev_o[k])      # F_k holds theta_{i-1}; the stores of replica k are free again
+                tick_map_priority(self.players[k].env)      # (both replicas roll over ONE shard: its table, on this stream)
                 g_r.replay()
                 self.ev_r[k].record(self.sR)
             self.pending = (k, g_l)
@@ -834,6 +855,7 @@ def train(rank, args, shared_model, optimizer, train_modes, n_iters, env=None):
     try:
         while True:
             t0 = time.time()
+            tick_map_priority(player.env)
             rollout(player, args.num_steps)
             training_mode = train_modes[rank]
             policy_loss, value_loss, entropies, pred_loss = player.optimize(

@@ -341,6 +341,7 @@ class VecTrack2D(object):
         self.map_side = 81 if ((map_type == "Maze") if map_type_per_env is None
                                else bool((np.asarray(map_type_per_env) == 1).all())) else 82
         self.map_bank, self.bank_select = None, None
+        self.map_priority_enabled = False
         if obs_type == "Full":   # track_1v1.py:254-256: Box(shape=(1, S, S)); S = 81 for Maze maps, else 82
             all_maze = (map_type == "Maze") if map_type_per_env is None else bool((np.asarray(map_type_per_env) == 1).all())
             self.obs_hw = (81, 81) if all_maze else (82, 82)
@@ -519,6 +520,15 @@ class VecTrack2D(object):
         assert idx.is_cuda and idx.dtype == torch.int32 and idx.is_contiguous() and idx.numel() == self.num_envs
         map_bank.lib().t2d_map_bank_index(self.h, C.c_void_p(idx.data_ptr()), self._stream())
         return idx
+
+    # -- prioritized map replay (include/track2d_bank_prio.h) --------------------------------------------------
+    def enable_map_priority(self):
+        """After attach_map_bank and before the first reset: the handle draws every episode's map from a weight table (uniform
+        until map_priority.MapPriority sets one), remembers what it drew (map_index() reads that) and keeps per-map accounts of
+        finished episodes. Such a handle takes no snapshots."""
+        from . import map_priority
+        map_priority.lib().t2d_bank_prio_enable(self.h, self._stream())
+        self.map_priority_enabled = True
 
     # -- heuristic players (include/track2d_heuristic.h) -------------------------------------------------------
     def heuristic_actions(self, roles=("pursuit", "evade"), out=None, dist=None):

@@ -52,7 +52,8 @@ int t2d_map_bank_attach(t2d_handle *h, const uint8_t *maps_host, const int32_t *
                         void *stream);
 
 /* The bank index of every env's current episode, by the rule above from episode[e]: idx_dev [N] i32. One launch on `stream`:
- * no synchronisation, no allocation, capturable. T2D_ERR_STATE without a bank or before the first reset. */
+ * no synchronisation, no allocation, capturable. T2D_ERR_STATE without a bank or before the first reset. (On a handle with
+ * priorities, track2d_bank_prio.h, the index is what the table drew for the episode, read from the handle's index ring.) */
 int t2d_map_bank_index(t2d_handle *h, int32_t *idx_dev, void *stream);
 
 /* K, or 0 without a bank. */

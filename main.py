@@ -142,6 +142,22 @@ parser.add_argument('--bank-select', default='random', choices=('random', 'cycle
 parser.add_argument('--eval-map-bank', default=None, metavar='FILE',
                     help='run the evaluation rounds (--env-base) on the maps of this bank file, in cycle order; with at most 64 '
                          'maps every round also writes test/map/<idx>/eps_len and test/map/<idx>/reward0')
+parser.add_argument('--map-priority', default=None, choices=('tracker', 'target'), metavar='ROLE',
+                    help='--map-bank: prioritized map replay (Jiang et al., 2021) — keep a per-map score of the training episodes '
+                         'on the device and serve the maps that are hard for ROLE (tracker or target), and the ones not seen for '
+                         'long, more often (one more launch per rollout, three per refresh); every --log-every record writes '
+                         'train/map_priority/* and <log-dir>/map_priority.npz. Not with --save-shard-state / --load-shard-state')
+parser.add_argument('--map-priority-every', type=int, default=10, metavar='M',
+                    help='--map-priority: refresh the weight table every M iterations')
+parser.add_argument('--map-priority-beta', type=float, default=0.1, metavar='B',
+                    help='--map-priority: temperature of the rank prioritisation, weight ~ rank^(-1/B) (0.1: the paper\'s setting, '
+                         'not tuned for this task)')
+parser.add_argument('--map-priority-rho', type=float, default=0.1, metavar='R',
+                    help='--map-priority: share of the staleness term in the weights (0.1: the paper\'s setting, not tuned here)')
+parser.add_argument('--map-priority-alpha', type=float, default=1.0, metavar='A',
+                    help='--map-priority: how much of a map\'s score its latest episodes replace (1.0: all of it)')
+parser.add_argument('--map-priority-load', default=None, metavar='FILE',
+                    help='--map-priority: continue the table of an earlier run\'s map_priority.npz')
 parser.add_argument('--save-shard-state', dest='save_shard_state', action='store_true',
                     help='write the env shard and the players\' recurrent rows to <log-dir>/shard-<rank>.pt after every evaluation '
                          'round and at exit (env snapshot blob of include/track2d_state.h, hxs, cxs, episode lengths, done flags, '
@@ -160,6 +176,16 @@ if __name__ == '__main__':
                      "args.adv_step there without defining the flag and stops with an AttributeError at the first switch")
     if args.max_grad_norm is not None and args.max_grad_norm <= 0:
         parser.error("--max-grad-norm must be positive")
+    if args.map_priority is not None and args.map_bank is None:
+        parser.error("--map-priority needs --map-bank: the priorities are over the maps of a bank")
+    if args.map_priority is not None and (args.save_shard_state or args.load_shard_state is not None):
+        parser.error("--map-priority cannot be combined with --save-shard-state / --load-shard-state: a prioritised env handle "
+                     "takes no snapshots (its index ring and table are not part of one)")
+    if args.map_priority is None and args.map_priority_load is not None:
+        parser.error("--map-priority-load needs --map-priority")
+    if args.map_priority_every < 1 or args.map_priority_beta <= 0 or not 0 <= args.map_priority_rho <= 1 \
+            or not 0 <= args.map_priority_alpha <= 1:
+        parser.error("--map-priority-every must be >= 1, --map-priority-beta > 0, --map-priority-rho and -alpha in [0, 1]")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     # (GPU_MAX_HW_QUEUES for the single-GPU pipelined schedule was decided before torch was imported: _wants_two_hw_queues)
     rank = int(os.environ.get("RANK", "0"))
@@ -197,6 +223,9 @@ if __name__ == '__main__':
     if args.sight_stats:
         from active_tracking_rl_amd.sight_stats import SightStats
         sight_stats = SightStats(player.env, device)
+    map_prio = getattr(player.env, "map_priority", None)     # (--map-priority: created with the env shard, create_env)
+    if map_prio is not None and args.map_priority_load is not None:
+        map_prio.load_state_dict(args.map_priority_load)
     if args.load_model_dir is not None:
         saved_state = torch.load(args.load_model_dir, map_location=lambda storage, loc: storage)
         player.model.load_state_dict(saved_state)
@@ -271,7 +300,8 @@ if __name__ == '__main__':
         if step is not None:
             stats = step(train_modes[rank])                 # one hipGraph per training mode (test.py:84-92 schedule)
         else:
-            from active_tracking_rl_amd.train import rollout
+            from active_tracking_rl_amd.train import rollout, tick_map_priority
+            tick_map_priority(player.env)
             rollout(player, args.num_steps)
             stats = player.optimize(None, optimizer, player.model, train_modes[rank], device)
         it += 1
@@ -292,6 +322,8 @@ if __name__ == '__main__':
                 track_stats.record(writer, it * args.num_steps * player.num_envs, rank, args.log_dir)
             if sight_stats is not None:
                 sight_stats.record(writer, it * args.num_steps * player.num_envs, rank, args.log_dir)
+            if map_prio is not None:
+                map_prio.record(writer, it * args.num_steps * player.num_envs, rank, args.log_dir)
             writer.flush()
             t_log, it_log = time.time(), it
         if it % args.test_every == 0 or it > args.max_step:
