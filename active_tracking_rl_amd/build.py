@@ -16,7 +16,7 @@ SOURCES = ["track2d_hip.hip", "stem_hip.hip", "policy_hip.hip", "lstm_hip.hip", 
            "actor_step_hip.hip", "pair_gemm_hip.hip", "bptt_hip.hip", "driver_hip.hip", "gate_cell_hip.hip", "episode_stats_hip.hip",
            "gru_hip.hip", "render_hip.hip", "tracking_stats_hip.hip", "state_hip.hip", "stem_full_hip.hip", "heuristic_hip.hip",
            "sight_stats_hip.hip", "occlusion_hip.hip", "np_mode.cpp", "lt_gemm.cpp"]
-HEADERS = ["t2d_device.h", os.path.join("..", "..", "include", "track2d.h"),
+HEADERS = ["t2d_device.h", "t2d_rooms_rule.h", os.path.join("..", "..", "include", "track2d.h"),
            os.path.join("..", "..", "include", "atr_policy.h"), "atr_sample.h", "atr_cell.h",
            os.path.join("..", "..", "include", "track2d_np.h"), os.path.join("..", "..", "include", "atr_eval.h"),
            os.path.join("..", "..", "include", "atr_stats.h"), os.path.join("..", "..", "include", "atr_gru.h"),

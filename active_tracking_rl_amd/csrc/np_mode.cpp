@@ -402,6 +402,7 @@ extern "C" const char *t2d_np_last_error(void) { return g_err; }
 extern "C" int t2d_np_create(int map_type, int target_mode, int level, uint32_t seed, t2d_np **out)
 {
     if (!out) return fail(-1, "t2d_np_create: null argument");
+    if (map_type == 3) return fail(-1, "t2d_np_create: Rooms maps (map_type 3) are not a reference generator: no numpy-stream mode");
     if (map_type < 0 || map_type > 2 || target_mode < 0 || target_mode > 5 || level < 0 || level > 15)
         return fail(-1, "t2d_np_create: map_type %d / target_mode %d / level %d out of range", map_type, target_mode, level);
     t2d_np *e = new (std::nothrow) t2d_np();

@@ -10,6 +10,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "t2d_rooms_rule.h"
 
 namespace t2d {
 
@@ -18,9 +19,9 @@ constexpr int kRowWords = 3;
 constexpr int kWavesPerBlock = 4; // 256-thread workgroups: 4 envs per block
 constexpr int kObsPerEnv = 338;   // 2 agents x 13 x 13
 
-enum : int { MAP_BLOCK = 0, MAP_MAZE = 1, MAP_EMPTY = 2 };
+enum : int { MAP_BLOCK = 0, MAP_MAZE = 1, MAP_EMPTY = 2, MAP_ROOMS = 3 };
 enum : int { TGT_ADV = 0, TGT_PZR = 1, TGT_FAR = 2, TGT_NAV = 3, TGT_RAM = 4, TGT_RPF = 5 };
-enum : uint32_t { STREAM_MAP = 0, STREAM_SPAWN = 1, STREAM_TARGET = 2, STREAM_ACTION = 7 };
+enum : uint32_t { STREAM_MAP = 0, STREAM_SPAWN = 1, STREAM_TARGET = 2, STREAM_ROOMS = 3, STREAM_ACTION = 7 };
 
 // ---- wave-level helpers -----------------------------------------------------------------------------
 __device__ __forceinline__ void wave_lds_sync()
@@ -262,6 +263,79 @@ __device__ __forceinline__ void gen_block(uint32_t *tile, int lane, S &ms, doubl
         uint32_t c = perm6400(rk, (uint32_t)i);
         uint32_t row = c / 80u + 1u, col = c - (c / 80u) * 80u + 1u;
         atomicOr(&tile[row * kRowWords + (col >> 5)], 1u << (col & 31u));
+    }
+    wave_lds_sync();
+    tile_border(tile, 82, lane);
+    wave_lds_sync();
+}
+
+// Rooms maps (T2D_MAP_ROOMS, include/track2d.h; the rule is t2d_rooms_rule.h, restated in tests/rooms_spec.py): axis-aligned
+// rooms joined by one-cell doorways, grown by recursive splitting of the interior. A region's random words are one Philox block
+// keyed by the region's own rectangle (stream STREAM_ROOMS), so the regions waiting to be split are independent: ONE LANE PER
+// REGION, breadth first over a queue in LDS (`queue`: kRoomsQueue words, the move log of the maze generator, idle on a
+// non-Maze env). A chunk of up to 64 queued regions is split at once — lane-private Philox and rule, ballot + prefix popcount
+// to append the children behind the queue's tail — and every lane lays its own wall: a horizontal wall is at most three word
+// masks, a vertical one a bit per row; the doors are cleared afterwards by the same lane (the DS operations of a wave execute
+// in order). Walls of different regions never share a cell, so regions need no ordering among themselves.
+// Every loop has a fixed trip bound: a chunk takes at least one region off the queue and the queue never holds more than
+// kRoomsQueue regions, so the chunk loop runs at most kRoomsQueue times whatever the data; a full queue ends generation with
+// the map as it stands (connected at every moment); a vertical wall is at most 80 rows.
+constexpr int kRoomsQueue = t2d_rooms::kMaxRegions;
+static_assert(kRoomsQueue <= 39 * 39, "the Rooms region queue lives in the maze generator's move log");
+__device__ __forceinline__ void gen_rooms(uint32_t *tile, int lane, uint32_t k0, uint32_t k1, uint32_t episode, uint32_t genv,
+                                          int level, uint32_t *queue)
+{
+    tile_clear(tile, lane);
+    int m = 3 + 2 * level;
+    if (level == 0) {
+        const u32x4 p = philox4x32_10(k0, k1, t2d_rooms::kParamWord, episode, genv, STREAM_ROOMS);
+        m = t2d_rooms::min_side(0, p.x);
+    }
+    m = uni(m);
+    if (lane == 0) queue[0] = t2d_rooms::region_word(t2d_rooms::kRoot0, t2d_rooms::kRoot0, t2d_rooms::kRoot1, t2d_rooms::kRoot1);
+    wave_lds_sync();
+    int head = 0, tail = 1;
+#pragma unroll 1
+    for (int it = 0; it < kRoomsQueue; it++) {
+        if (head >= tail) break;
+        const int i = head + lane;
+        const bool act = i < tail;
+        const uint32_t reg = act ? queue[i] : 0u;
+        const u32x4 x = philox4x32_10(k0, k1, reg, episode, genv, STREAM_ROOMS);
+        const t2d_rooms::Split sp = t2d_rooms::split(reg, m, x.x, x.y, x.z, x.w);
+        const bool cut = act && sp.final_ == 0;
+        const unsigned long long cuts = __ballot(cut);
+        const int ncut = uni((int)__popcll(cuts));
+        if (tail + 2 * ncut > kRoomsQueue) break;                 // full queue: the map stays as it stands
+        if (cut) {
+            const int at = tail + 2 * (int)__popcll(cuts & ((1ull << lane) - 1ull));
+            queue[at] = sp.child0;
+            queue[at + 1] = sp.child1;
+            if (sp.horizontal) {                                  // row t, columns b0 .. b1
+                uint32_t *w = tile + sp.t * kRowWords;
+#pragma unroll
+                for (int j = 0; j < 3; j++) {
+                    const int lo = max(sp.b0, 32 * j), hi = min(sp.b1, 32 * j + 31);
+                    if (lo <= hi) atomicOr(&w[j], ((2u << (hi - lo)) - 1u) << (lo - 32 * j));
+                }
+                atomicAnd(&w[sp.door1 >> 5], ~(1u << (sp.door1 & 31)));
+                atomicAnd(&w[sp.door2 >> 5], ~(1u << (sp.door2 & 31)));
+            } else {                                              // column t, rows b0 .. b1
+                uint32_t *w = tile + (sp.t >> 5);
+                const uint32_t bit = 1u << (sp.t & 31);
+#pragma unroll 1
+                for (int k = 0; k < 80; k++) {
+                    const int r = sp.b0 + k;
+                    if (r > sp.b1) break;
+                    atomicOr(&w[r * kRowWords], bit);
+                }
+                atomicAnd(&w[sp.door1 * kRowWords], ~bit);
+                atomicAnd(&w[sp.door2 * kRowWords], ~bit);
+            }
+        }
+        head = min(head + 64, tail);
+        tail += 2 * ncut;
+        wave_lds_sync();
     }
     wave_lds_sync();
     tile_border(tile, 82, lane);

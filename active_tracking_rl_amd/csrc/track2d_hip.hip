@@ -339,6 +339,8 @@ __device__ __forceinline__ void generate_episode(const DevState &s, int e, uint3
     } else if (map_type == MAP_BLOCK) {
         double r = level > 0 ? (double)level * 0.05 : 0.15 * ms.next_double();
         gen_block(tile, lane, ms, r);
+    } else if (map_type == MAP_ROOMS) {     // keyed by region, not by the MAP stream; the move log of the maze generator is its queue
+        gen_rooms(tile, lane, s.k0, s.k1, episode, genv, level, mlog);
     } else {
         gen_block(tile, lane, ms, 0.0);
     }
@@ -2572,6 +2574,7 @@ struct t2d_handle {
     uint32_t random_step;
     bool has_navmode;  // some env has the Nav target (its next plan is prefetched once per stamp window)
     bool has_rpfmode;  // some env has the RPF patrol target: those handles stay on the general step kernel (k_env)
+    bool has_rooms = false;    // some env has Rooms maps (T2D_MAP_ROOMS): the numpy-stream mode is refused
     uint32_t gen_every; // shortest possible episode = longest admissible generator period, in steps
     // Step stamps run 1..cycle; the cycle is one window of gen_every steps (generator in order on the caller's
     // stream) or, with the asynchronous generator, two windows of gen_every / 2: the slots consumed in window w are
@@ -2661,14 +2664,14 @@ extern "C" int t2d_create(const t2d_config *cfg, t2d_handle **out)
     const int n = cfg->num_envs;
     std::vector<uint32_t> hcfg((size_t)n);
     bool has_nav = false, has_rpf = false, has_ram = false, has_navmode = false, has_rpfmode = false;
-    int n_maze = 0;
+    int n_maze = 0, n_rooms = 0;
     if (cfg->obs_type > T2D_OBS_FULL) return fail(T2D_ERR_INVALID, "t2d_create: obs_type %u", cfg->obs_type);
     if (cfg->action_type > T2D_ACTIONS_MOORE) return fail(T2D_ERR_INVALID, "t2d_create: action_type %u", cfg->action_type);
     for (int i = 0; i < n; i++) {
         uint32_t mt = cfg->map_type_per_env ? cfg->map_type_per_env[i] : cfg->map_type;
         uint32_t tm = cfg->target_mode_per_env ? cfg->target_mode_per_env[i] : cfg->target_mode;
         uint32_t lv = cfg->level_per_env ? cfg->level_per_env[i] : cfg->level;
-        if (mt > T2D_MAP_EMPTY) return fail(T2D_ERR_INVALID, "t2d_create: map_type %u (env %d)", mt, i);
+        if (mt > T2D_MAP_ROOMS) return fail(T2D_ERR_INVALID, "t2d_create: map_type %u (env %d)", mt, i);
         if (tm > T2D_TGT_EXT) return fail(T2D_ERR_INVALID, "t2d_create: target_mode %u (env %d)", tm, i);
         has_nav = has_nav || tm == T2D_TGT_NAV || tm == T2D_TGT_RPF;
         has_rpf = has_rpf || tm == T2D_TGT_RPF || tm == T2D_TGT_EXT;   // agents may stand on walls
@@ -2676,6 +2679,10 @@ extern "C" int t2d_create(const t2d_config *cfg, t2d_handle **out)
         has_navmode = has_navmode || tm == T2D_TGT_NAV;
         has_rpfmode = has_rpfmode || tm == T2D_TGT_RPF;
         n_maze += mt == T2D_MAP_MAZE;
+        n_rooms += mt == T2D_MAP_ROOMS;
+        // the four static patrol cells would land on the walls of a Rooms map
+        if (mt == T2D_MAP_ROOMS && tm == T2D_TGT_RPF)
+            return fail(T2D_ERR_INVALID, "t2d_create: Rooms maps have no RPF patrol target (env %d)", i);
         if (lv > 15) return fail(T2D_ERR_INVALID, "t2d_create: level %u (env %d)", lv, i);
         // the scripted targets plan in the four-move table: RamAgent would draw from 8 actions (navigator.py:74-75) and the
         // Navigator's A* fails outright in the reference (Astar_solver.py:138,163-169 index a 4-entry table with 8 actions)
@@ -2692,6 +2699,7 @@ extern "C" int t2d_create(const t2d_config *cfg, t2d_handle **out)
     h->device = cfg->device;
     h->reset_done = false; h->primed = false; h->has_nav = has_nav; h->has_rpf = has_rpf; h->has_ram = has_ram;
     h->has_navmode = has_navmode; h->has_rpfmode = has_rpfmode; h->has_maze = n_maze > 0;
+    h->has_rooms = n_rooms > 0;
     h->random_step = 0; h->phase = 0;
     h->gen_async = false; h->pending[0] = h->pending[1] = false;
     h->gen_stream = nullptr; h->ev_fork = nullptr; h->ev_join[0] = h->ev_join[1] = nullptr;
@@ -3066,6 +3074,7 @@ extern "C" int t2d_np_attach(t2d_handle *h, const uint32_t *states_host)
     if (!h || !states_host) return fail(T2D_ERR_INVALID, "t2d_np_attach: null argument");
     if (h->primed || h->reset_done) return fail(T2D_ERR_STATE, "t2d_np_attach: attach the streams before the first t2d_reset");
     if (h->bank.tiles) return fail(T2D_ERR_INVALID, "t2d_np_attach: the handle has a map bank (t2d_map_bank_attach)");
+    if (h->has_rooms) return fail(T2D_ERR_INVALID, "t2d_np_attach: the handle has Rooms maps: the numpy streams drive the reference's generators only");
     if ((h->has_ram || h->has_navmode || h->has_rpfmode) && h->s.auto_reset)
         return fail(T2D_ERR_INVALID, "t2d_np_attach: a Ram / Nav / RPF target draws from the stream between resets, so its next episode "
                                      "cannot be generated ahead of the in-launch auto-reset: create the handle with auto_reset = 0 "

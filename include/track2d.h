@@ -36,7 +36,18 @@ typedef enum {
 } t2d_status;
 
 /* map_type / target_mode values: the kwargs of the registry, G/__init__.py:3-18 */
-enum { T2D_MAP_BLOCK = 0, T2D_MAP_MAZE = 1, T2D_MAP_EMPTY = 2 };
+enum { T2D_MAP_BLOCK = 0, T2D_MAP_MAZE = 1, T2D_MAP_EMPTY = 2,
+       /* not a reference map type: 82 x 82 floor plans of axis-aligned rooms joined by one-cell doorways, connected by
+        * construction. The interior (1, 1, 80, 80) is split recursively: a region of h x w cells with random words X, Y, Z, W =
+        * philox4x32_10(counter = (r0 | c0 << 7 | r1 << 14 | c1 << 21, episode, global env id, 3), key = seed) is final if
+        * h <= 4m, w <= 4m and ((X >> 8) & 7) == 0, or if no even line t with a0 + m <= t <= a1 - m exists along the split axis
+        * (rows if h > w, columns if w > h, rows iff (X & 1) == 0 on a tie); else the wall is line t = the pick(Y)-th such line,
+        * with doors at the pick(Z)-th and (wall length >= 32) pick(W)-th odd position across it, pick(word, n) = word * n >> 32.
+        * m = 3 + 2 level, or 5 + 2 pick(P.x, 4) at level 0 (P: the block with counter word 0 = 0xffffffff). A pure function of
+        * (seed, global env id, episode, level); the MAP / SPAWN / TARGET streams are untouched. The arithmetic is
+        * csrc/t2d_rooms_rule.h, restated in tests/rooms_spec.py. Refused with an RPF target (the static patrol cells would land
+        * on walls) and by the numpy-stream mode (t2d_np_attach / t2d_np_create: the reference's generators only). */
+       T2D_MAP_ROOMS = 3 };
 enum { T2D_TGT_ADV = 0, T2D_TGT_PZR = 1, T2D_TGT_FAR = 2, T2D_TGT_NAV = 3, T2D_TGT_RAM = 4, T2D_TGT_RPF = 5,
        /* not a registry mode: the target's action always comes from the caller (w_p = 0 like Adv/Nav/Ram/RPF) and the
         * agents may be injected on wall cells, as the reference's RPF spawn can be (track_1v1.py:233-236). Used by the
