@@ -64,9 +64,23 @@ parser.add_argument('--map-bank', default=None, metavar='FILE',
 parser.add_argument('--occlusion', dest='occlusion', action='store_true',
                     help='walls hide what is behind them: in both players\' 13 x 13 windows every cell whose line of sight from '
                          'the centre is blocked by a wall reads 5 ("unseen"); --graphed-eval falls back to the eager evaluator')
+parser.add_argument('--fov', type=int, default=None, choices=(90, 180, 270), metavar='DEG',
+                    help='a player sees only a cone of DEG degrees (90, 180 or 270) ahead: it faces the way of its last move, and '
+                         'every cell of its 13 x 13 window outside the cone and farther than --fov-near from the centre reads 5 '
+                         '("unseen"); a new episode starts looking all round. --graphed-eval falls back to the eager evaluator. '
+                         'The heuristic players (--heuristic-tracker, --heuristic-target) read true state and are not blinded. '
+                         'Not with --render')
+parser.add_argument('--fov-target', type=int, default=None, choices=(90, 180, 270, 360), metavar='DEG',
+                    help='--fov: the target\'s aperture (default: as --fov; 360: the target is not restricted)')
+parser.add_argument('--fov-near', type=int, default=1, choices=tuple(range(7)), metavar='N',
+                    help='--fov: cells within N of the centre (Chebyshev) stay visible all round (default: 1)')
 
 if __name__ == '__main__':
     args = parser.parse_args()
+    if args.fov is None and args.fov_target is not None:
+        parser.error("--fov-target needs --fov")
+    if args.fov is not None and args.render:
+        parser.error("--fov cannot be combined with --render: the drawn tracker's window would show what the tracker does not see")
     build.build()
     check_path(args.log_dir)
     name = '{}_mon_log'.format(args.env)

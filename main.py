@@ -134,6 +134,17 @@ parser.add_argument('--occlusion', dest='occlusion', action='store_true',
                     help='walls hide what is behind them: in both players\' 13 x 13 windows every cell whose line of sight from '
                          'the centre is blocked by a wall reads 5 ("unseen"), in training and in the evaluation rounds (one more '
                          'launch per env step, and the env step runs outside the policy step\'s last launch)')
+parser.add_argument('--fov', type=int, default=None, choices=(90, 180, 270), metavar='DEG',
+                    help='a player sees only a cone of DEG degrees (90, 180 or 270) ahead: it faces the way of its last move, and '
+                         'every cell of its 13 x 13 window outside the cone and farther than --fov-near from the centre reads 5 '
+                         '("unseen"); a new episode starts looking all round. In training and in the evaluation rounds (one more '
+                         'launch per env step, after --occlusion\'s where both are given, and the env step runs outside the policy '
+                         'step\'s last launch). The heuristic players of --eval-heuristic read true state and are not blinded. '
+                         'Not with --tracking-stats, --sight-stats or --render')
+parser.add_argument('--fov-target', type=int, default=None, choices=(90, 180, 270, 360), metavar='DEG',
+                    help='--fov: the target\'s aperture (default: as --fov; 360: the target is not restricted)')
+parser.add_argument('--fov-near', type=int, default=1, choices=tuple(range(7)), metavar='N',
+                    help='--fov: cells within N of the centre (Chebyshev) stay visible all round (default: 1)')
 parser.add_argument('--map-bank', default=None, metavar='FILE',
                     help='train on the maps of a bank file (.npz / .txt: python -m active_tracking_rl_amd.map_bank) instead of '
                          'generated ones: every episode of every env, the in-launch auto-reset included, takes its map from the bank')
@@ -176,6 +187,13 @@ if __name__ == '__main__':
                      "args.adv_step there without defining the flag and stops with an AttributeError at the first switch")
     if args.max_grad_norm is not None and args.max_grad_norm <= 0:
         parser.error("--max-grad-norm must be positive")
+    if args.fov is None and args.fov_target is not None:
+        parser.error("--fov-target needs --fov")
+    if args.fov is not None and (args.tracking_stats or args.sight_stats):
+        parser.error("--fov cannot be combined with --tracking-stats / --sight-stats: their tables assume that the tracker sees "
+                     "the target exactly when the target sees the tracker, which a cone does not keep")
+    if args.fov is not None and args.render:
+        parser.error("--fov cannot be combined with --render: the drawn tracker's window would show what the tracker does not see")
     if args.map_priority is not None and args.map_bank is None:
         parser.error("--map-priority needs --map-bank: the priorities are over the maps of a bank")
     if args.map_priority is not None and (args.save_shard_state or args.load_shard_state is not None):
