@@ -182,7 +182,7 @@ class Agent(object):
                                             and (obs0.numel() * obs0.element_size()) % 4 == 0)))
         if want_cache:
             # will every step's env.step run inside the policy step's last launch? (action_rollout asks the same question per
-            # step; envs that decline — RPF targets, 'Full' observations, --rescale, stacked frames, --occlusion, --fov, NumpyVecEnv — step on
+            # step; envs that decline — RPF targets, 'Full' observations, --rescale, stacked frames, --occlusion, --fov, --footprints, NumpyVecEnv — step on
             # their own, and the cache must then not take the form whose hidden rows only k_act_step writes)
             env_fused = (self._buf is not None and hasattr(self.env, "fused_step_out") and num_steps >= 1
                          and self.env.fused_step_out((self._buf[0][1], self._buf[1][0], self._buf[2][0])) is not None)
@@ -365,7 +365,7 @@ class Agent(object):
         sampler = getattr(self.model, "_sampler", None)
         if sampler is not None:
             d["sampler_counter"], d["sampler_seed"] = sampler.counter.cpu().clone(), int(sampler.seed)
-        for key in ("_frames", "_inv_flags", "_inv_fresh", "_facing"):
+        for key in ("_frames", "_inv_flags", "_inv_fresh", "_facing", "_trail"):
             t = getattr(self.env, key, None)
             if t is not None:
                 d["env" + key] = t.cpu().clone()
@@ -399,6 +399,11 @@ class Agent(object):
                 setattr(self.env, key, d["env" + key].to(self.device))
         if "env_facing" in d and getattr(self.env, "_facing", None) is not None:       # (--fov: in place, the env keeps its tensor)
             self.env._facing.copy_(d["env_facing"].to(self.device))
+        if "env_trail" in d and getattr(self.env, "_trail", None) is not None:         # (--footprints: in place, likewise)
+            if tuple(d["env_trail"].shape) != tuple(self.env._trail.shape):
+                raise ValueError("load_shard_state: the saved trail has shape %s, this env's %s (another --footprints K)"
+                                 % (tuple(d["env_trail"].shape), tuple(self.env._trail.shape)))
+            self.env._trail.copy_(d["env_trail"].to(self.device))
         self.state = self.env.observe()
 
     def clear_actions(self):

@@ -74,6 +74,14 @@ parser.add_argument('--fov-target', type=int, default=None, choices=(90, 180, 27
                     help='--fov: the target\'s aperture (default: as --fov; 360: the target is not restricted)')
 parser.add_argument('--fov-near', type=int, default=1, choices=tuple(range(7)), metavar='N',
                     help='--fov: cells within N of the centre (Chebyshev) stay visible all round (default: 1)')
+parser.add_argument('--footprints', type=int, default=None, choices=tuple(range(1, 64)), metavar='K',
+                    help='players leave a trail the other can see: each player leaves footprints on the last K (1 .. 63) cells it '
+                         'stepped off, and the other player\'s 13 x 13 window shows them as 6 wherever it could see a free cell '
+                         'there (a print behind a wall or outside the cone stays hidden); a new episode starts with no prints. '
+                         '--graphed-eval falls back to the eager evaluator. Not with --render')
+parser.add_argument('--footprints-for', default=None, choices=('tracker', 'target', 'both'), metavar='WHO',
+                    help='--footprints: whose window shows the other\'s prints: tracker, target or both (default: tracker; a '
+                         'scripted Ram / Nav / RPF target reads no window: tracker only)')
 
 if __name__ == '__main__':
     args = parser.parse_args()
@@ -81,6 +89,17 @@ if __name__ == '__main__':
         parser.error("--fov-target needs --fov")
     if args.fov is not None and args.render:
         parser.error("--fov cannot be combined with --render: the drawn tracker's window would show what the tracker does not see")
+    if args.footprints is None and args.footprints_for is not None:
+        parser.error("--footprints-for needs --footprints")
+    if args.footprints is not None and args.render:
+        parser.error("--footprints cannot be combined with --render: the drawn tracker's window comes from the renderer's own "
+                     "cells and would not show the prints")
+    if args.footprints_for is None:
+        args.footprints_for = "tracker"
+    if (args.footprints is not None and args.footprints_for != "tracker" and '2D' in args.env
+            and registry.spec(args.env)["target_mode"] in ("Ram", "Nav", "RPF")):
+        parser.error("--footprints-for %s: the scripted target of %s reads no window, only the tracker's is painted there: use "
+                     "--footprints-for tracker, or an id whose target is a player" % (args.footprints_for, args.env))
     build.build()
     check_path(args.log_dir)
     name = '{}_mon_log'.format(args.env)

@@ -145,6 +145,14 @@ parser.add_argument('--fov-target', type=int, default=None, choices=(90, 180, 27
                     help='--fov: the target\'s aperture (default: as --fov; 360: the target is not restricted)')
 parser.add_argument('--fov-near', type=int, default=1, choices=tuple(range(7)), metavar='N',
                     help='--fov: cells within N of the centre (Chebyshev) stay visible all round (default: 1)')
+parser.add_argument('--footprints', type=int, default=None, choices=tuple(range(1, 64)), metavar='K',
+                    help='players leave a trail the other can see: each player leaves footprints on the last K (1 .. 63) cells it '
+                         'stepped off, and the other player\'s 13 x 13 window shows them as 6 wherever it could see a free cell '
+                         'there (a print behind a wall or outside the cone stays hidden); a new episode starts with no prints. '
+                         'In training and in the evaluation rounds (one more launch per env step, after --occlusion\'s and --fov\'s where they are given, and the env step runs outside the policy step\'s last launch). Not with --tracking-stats, --sight-stats or --render')
+parser.add_argument('--footprints-for', default=None, choices=('tracker', 'target', 'both'), metavar='WHO',
+                    help='--footprints: whose window shows the other\'s prints: tracker, target or both (default: tracker; a '
+                         'scripted Ram / Nav / RPF target reads no window: tracker only)')
 parser.add_argument('--map-bank', default=None, metavar='FILE',
                     help='train on the maps of a bank file (.npz / .txt: python -m active_tracking_rl_amd.map_bank) instead of '
                          'generated ones: every episode of every env, the in-launch auto-reset included, takes its map from the bank')
@@ -194,6 +202,23 @@ if __name__ == '__main__':
                      "the target exactly when the target sees the tracker, which a cone does not keep")
     if args.fov is not None and args.render:
         parser.error("--fov cannot be combined with --render: the drawn tracker's window would show what the tracker does not see")
+    if args.footprints is None and args.footprints_for is not None:
+        parser.error("--footprints-for needs --footprints")
+    if args.footprints is not None and (args.tracking_stats or args.sight_stats):
+        parser.error("--footprints cannot be combined with --tracking-stats / --sight-stats: their bins were written for windows "
+                     "over {0, 1, 2, 4, 5}, and nobody has examined what a 6 does to them")
+    if args.footprints is not None and args.render:
+        parser.error("--footprints cannot be combined with --render: the drawn tracker's window comes from the renderer's own "
+                     "cells and would not show the prints")
+    if args.footprints_for is None:
+        args.footprints_for = "tracker"
+    if args.footprints is not None and args.footprints_for != "tracker":
+        from active_tracking_rl_amd import registry
+        for flag, env_id in (("--env", args.env), ("--env-base", args.env_base)):
+            if '2D' in env_id and registry.spec(env_id)["target_mode"] in ("Ram", "Nav", "RPF"):
+                parser.error("--footprints-for %s: the scripted target of %s %s reads no window, only the tracker's is painted "
+                             "there (the evaluation rounds run on --env-base): use --footprints-for tracker, or ids whose target "
+                             "is a player" % (args.footprints_for, flag, env_id))
     if args.map_priority is not None and args.map_bank is None:
         parser.error("--map-priority needs --map-bank: the priorities are over the maps of a bank")
     if args.map_priority is not None and (args.save_shard_state or args.load_shard_state is not None):
