@@ -34,6 +34,11 @@ FACTOR, FLOOR, ATEN_MAX, RESOLUTION = 4.0, 1e-6, 1e-4, 10.0
 # resolves: e is taken per player over all T steps, so an error confined to one step must reach ~sqrt(T) x 4e-6 of that
 # step's own norm (about 2e-5 at T = 20) to show — a done mask applied one step late moves the hidden rows of every env that
 # ended there by O(1), orders of magnitude above it; the cell kernels' own rounding does not reach it.
+# The GRU cores' cached step (k_gru_step, --fused-gru; tests/test_gru_learner_f64_gpu.py, 130 x 8 eager to 1024 x 4 captured)
+# measured e(hip) 1.91e-7 .. 2.30e-7 against e(aten32) 1.18e-7 .. 1.97e-7 (at most 1.8x): inside 4 e(aten32) already, so the GRU
+# cases use this floor as it is and no GRU_HIDDEN_FLOOR exists. Against it a done mask applied one step late still shows: with a
+# 37-step TimeLimit about 1 env in 37 ends at a given step, its next hidden row moves by O(1) of its norm, which is e ~ sqrt(1 / (37 T))
+# = 0.06 at T = 8 over the player's whole h_all — four orders of magnitude above the floor.
 HIDDEN_FLOOR = 4e-6
 
 
@@ -116,6 +121,8 @@ def build_reference_model(snap, dtype=torch.float64, device="cpu"):
             mod.use_fused = False
             mod._dense = None
     m.fused_sampling = False
+    # (a GRU model reads ATR_FUSED_GRU from the environment when it is built: the reference never takes the cached, env-fused step)
+    m.fused_gru_step = False
     return m
 
 
@@ -148,6 +155,7 @@ def reference(snap, mode, dtype=torch.float64, device="cpu", envs=None, model=No
             assert v.device.type == "cpu", k
     if model is None:
         model = build_reference_model(snap, dtype, dev)
+    assert not getattr(model, "fused_gru_step", False), "the reference model must not take the GRU cores' fused rollout step"
     blas = None
     if dev.type == "cuda":
         # (the floor's GEMMs on the BLAS library's classic kernels: the Lt heuristic's pick for some ragged shapes — the

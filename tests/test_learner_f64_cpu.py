@@ -53,6 +53,13 @@ def _per_step_run(network, aux, mode, draw="argmax"):
         torch.manual_seed(4)
         env = _RecordingEnv(range(N))
         model = build_model(env.observation_space, env.action_space, args, torch.device("cpu")).double()
+        if "gru" in network:
+            # (biases start at zero, where b_hn inside r * (W_hn h + b_hn) cannot tell: the GRU case moves every 1-D parameter)
+            g = torch.Generator().manual_seed(9)
+            with torch.no_grad():
+                for p in model.parameters():
+                    if p.dim() == 1:
+                        p.normal_(0, 0.1, generator=g)
         ag = Agent(model, env, args, None, torch.device("cpu"))
         ag.reset()
         rollout(ag, T, fast=False)
@@ -87,10 +94,13 @@ def _per_step_run(network, aux, mode, draw="argmax"):
 
 
 @pytest.mark.parametrize("mode", [-1, 0, 1])
-@pytest.mark.parametrize("network,aux", [("tat-maze-lstm", "reward"), ("maze-lstm", "none")])
+@pytest.mark.parametrize("network,aux", [("tat-maze-lstm", "reward"), ("maze-lstm", "none"), ("tat-maze-gru", "reward")])
 def test_float64_reference_equals_the_per_step_path(network, aux, mode, draw="argmax"):
     snap, grads, terms, loss = _per_step_run(network, aux, mode, draw)
     dones = snap["dones"]
+    assert snap["rnn_out"] == 128
+    if "gru" in network:        # (a GRU's cell state is never written: what tests/test_gru_learner_f64_gpu.py's snapshots hold too)
+        assert float(snap["c0"].abs().max()) == 0.0
     assert float(snap["h0"].abs().max()) > 0, "the window starts from a non-zero LSTM state"
     assert int(dones[:T - 1].sum()) >= 2 and len(set(np.nonzero(dones[:T - 1].numpy())[0].tolist())) >= 2, \
         "episode ends inside the window"
@@ -125,6 +135,21 @@ def test_bootstrap_draw_that_is_not_the_argmax_is_substituted(mode):
     ref_argmax = learner_f64.reference(dict(snap, boot_action=None), mode)
     assert learner_f64.rel_err(ref_argmax["boot_v"][:, 1], learner_f64.reference(snap, mode)["boot_v"][:, 1]) > 1e-6
     test_float64_reference_equals_the_per_step_path("tat-maze-lstm", "reward", mode, draw="argmin")
+
+
+def test_reference_model_never_takes_the_fused_gru_step(monkeypatch):
+    """model.py reads ATR_FUSED_GRU when a model is built: the reference's model has the switch off whatever the environment says,
+    and reference() refuses a model handed in with it on."""
+    snap, _, _, _ = _per_step_run("tat-maze-gru", "reward", -1)
+    monkeypatch.setenv("ATR_FUSED_GRU", "1")
+    args = default_args(network="tat-maze-gru")
+    env = FakeVecEnv(range(N))
+    assert build_model(env.observation_space, env.action_space, args, torch.device("cpu")).fused_gru_step is True
+    m = learner_f64.build_reference_model(snap)
+    assert m.fused_gru_step is False and m.gru_core and not m.cacheable_core
+    m.fused_gru_step = True
+    with pytest.raises(AssertionError, match="fused rollout step"):
+        learner_f64.reference(snap, -1, model=m)
 
 
 def test_env_subset_is_that_envs_share_of_the_gradient():

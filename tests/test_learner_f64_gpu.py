@@ -17,7 +17,10 @@ float64 gradient is zero (the untrained player in training modes 0 / 1) the buck
 
 Hidden sizes other than 128 (--rnn-out 64 / 96 / 256, maze-gru at 64) and tau != 1: the last test of the module and the mode -1 case
 of the 512-env test; their measured figures are in those tests' docstrings. With the tau factor removed from k_gae in a scratch build
-the 512-env mode -1 case fails (as do the tau != 1 cases of tests/test_fused_stem_gpu.py's GAE test)."""
+the 512-env mode -1 case fails (as do the tau != 1 cases of tests/test_fused_stem_gpu.py's GAE test).
+
+The GRU cores at R = 128 — the one-launch GRU BPTT, the --fused-gru cache, its fold, grouped and co-run paths — are held to the same
+rule with these helpers in tests/test_gru_learner_f64_gpu.py."""
 import numpy as np
 import pytest
 import torch
@@ -53,11 +56,20 @@ def _probe_forward(model):
     model.forward = forward
 
 
-def _make(env_id, n, network, aux, train_mode, steps=20, seed=31, max_steps=500, mixed=False, rnn_out=128, tau=None, gamma=None):
+BIAS_NOISE_SEED = 1234
+
+
+def _make(env_id, n, network, aux, train_mode, steps=20, seed=31, max_steps=500, mixed=False, rnn_out=128, tau=None, gamma=None,
+          fused_gru=False, bias_noise=False):
+    """fused_gru: the --fused-gru switch (the GRU cores' cached, env-fused rollout step). bias_noise: every 1-D parameter (the cell's
+    b_ih / b_hh — b_hn among them —, the fc and head biases: all zero at initialisation) drawn from N(0, 0.1) under a fixed seed, in
+    place (the parameters are views of the bucket's flat tensor), before any rollout, warm-up or capture."""
     from active_tracking_rl_amd import registry
     from active_tracking_rl_amd.environment import VecEnv
     from active_tracking_rl_amd.train import default_args, make_player
     over = dict(rnn_out=rnn_out)
+    if fused_gru:
+        over["fused_gru"] = True
     if tau is not None:
         over["tau"] = tau
     if gamma is not None:
@@ -72,8 +84,26 @@ def _make(env_id, n, network, aux, train_mode, steps=20, seed=31, max_steps=500,
         over["map_type_per_env"] = np.array([registry.MAP_CODE["Block" if i % 2 == 0 else "Maze"] for i in range(n)], np.uint8)
     env = VecEnv(env_id, n, device="cuda:0", seed=seed, obs_u8=True, **over)
     player, opt = make_player(args, torch.device("cuda:0"), 0, 1, env=env)
+    if bias_noise:
+        g = torch.Generator(device="cuda:0").manual_seed(BIAS_NOISE_SEED)
+        flat = opt.bucket.flat.data_ptr(), opt.bucket.flat.data_ptr() + opt.bucket.flat.numel() * 4
+        with torch.no_grad():
+            for p in player.model.parameters():
+                if p.dim() == 1:
+                    p.normal_(0, 0.1, generator=g)
+                    assert flat[0] <= p.data_ptr() < flat[1], "a parameter that left the bucket's flat tensor"
     _probe_boot(player.model)
     return player, opt, args
+
+
+def _snapshot(player, **kw):
+    """learner_f64.snapshot; on a GRU cache (model._new_cache_gru: h_all [2, T+1, N, R] as the LSTM cache lays it out, c_all the zero
+    tensor no launch writes, the bootstrap draw in cache.boot.actions[0]) the cell state it starts from must be exactly zero."""
+    snap = learner_f64.snapshot(player, **kw)
+    if getattr(player._cache, "gru", False):
+        assert float(snap["c0"].abs().max()) == 0.0 and float(player._cache.c_all.abs().max()) == 0.0, "a GRU cache's c_all is zero"
+        assert snap["h0"].shape == snap["c0"].shape == (2, player._cache.N, player._cache.h_all.shape[-1])
+    return snap
 
 
 def _window(it, player, opt, mode, max_iters=80):
@@ -153,15 +183,18 @@ def _references(snap, mode):
     return ref, floor, share
 
 
-def _run(player, opt, args, mode, label):
-    """Synchronous captured graph: >= 2 real iterations (the eager warm-up, kept), then the window."""
+def _run(player, opt, args, mode, label, spy=None):
+    """Synchronous captured graph: >= 2 real iterations (the eager warm-up, kept), then the window. spy (an object with a
+    `recording` flag): records while the warm-up iterations and the capture issue their launches, not after."""
     from active_tracking_rl_amd.train import GraphedIteration
     it = GraphedIteration(player, opt, args, mode=mode, keep_warmup_updates=True)
+    if spy is not None:
+        spy.recording = False
     it.run(mode)
     _window(it, player, opt, mode)
     # (R = 256: the bootstrap step is the model's own forward, whose draw _probe_forward kept)
     in_cache = getattr(player._cache, "boot", None) is not None
-    snap = learner_f64.snapshot(player, boot_action=None if (in_cache or not player.model.tat) else player.model.boot_action)
+    snap = _snapshot(player, boot_action=None if (in_cache or not player.model.tat) else player.model.boot_action)
     hip = _bucket_grads(player.model, opt.bucket)
     h = player._cache.h_all[:, 1:].transpose(0, 1)
     ref, floor, share = _references(snap, mode)
@@ -178,16 +211,20 @@ def test_headline_learner_synchronous_and_pipelined_against_float64():
     mode = -1
     player, opt, args = _make("Track2D-BlockPartialPZR-v0", 4096, "tat-maze-lstm", "reward", mode)
     try:
-        _headline(player, opt, args, mode)
+        _headline(player, opt, args, mode, "pzr4096")
+        cache = player._cache               # (the window's: nothing ran on the master after it)
+        assert cache.pre_all is not None and cache.fh_all is not None
     finally:
         player.env.close()
 
 
-def _headline(player, opt, args, mode):
+def _headline(player, opt, args, mode, label):
+    """One rollout window through the synchronous captured graph, then the same rollout transplanted into a PipelinedIteration
+    replica whose learner graph was captured with the co-run dW plan: one float64 reference for both. Returns the schedule."""
     from test_drivers_gpu import _transplant_rollout
     from active_tracking_rl_amd.train import GraphedIteration, PipelinedIteration
     it_p = PipelinedIteration(player, opt, args, mode=mode, serial=True)      # (first: it warms up eagerly on the master)
-    assert it_p.corun, "co-run dW is the pipelined learner's form at 4096 envs"
+    assert it_p.corun, "co-run dW is the pipelined learner's form from train.CORUN_MIN_ENVS envs up"
     it = GraphedIteration(player, opt, args, mode=mode, keep_warmup_updates=True)
     rep = it_p.players[0]
     _probe_boot(rep.model)
@@ -196,8 +233,8 @@ def _headline(player, opt, args, mode):
     it.run(mode)
     _window(it, player, opt, mode)
     cache = player._cache
-    assert cache.pre_all is not None and cache.fh_all is not None and player._buf[0].dtype == torch.uint8
-    snap = learner_f64.snapshot(player)
+    assert player._buf[0].dtype == torch.uint8
+    snap = _snapshot(player)
     hip_sync = _bucket_grads(player.model, opt.bucket)
     boot_sync = player.model.boot_probe.clone()
     h = cache.h_all[:, 1:].transpose(0, 1).clone()
@@ -212,9 +249,10 @@ def _headline(player, opt, args, mode):
     assert torch.equal(rep._cache.boot.actions[0], cache.boot.actions[0]), "the two bootstrap steps drew differently"
     hip_pipe = _bucket_grads(rep.model, it_p.buckets[0])
     ref, floor, share = _references(snap, mode)
-    _check("pzr4096 synchronous", ref, floor, share, mode, hip_sync, _stats(it.stats_by_mode[mode]), boot_sync, h)
-    _check("pzr4096 pipelined co-run", ref, floor, share, mode, hip_pipe, _stats(it_p.graphs[(mode, 0)][2]),
+    _check(label + " synchronous", ref, floor, share, mode, hip_sync, _stats(it.stats_by_mode[mode]), boot_sync, h)
+    _check(label + " pipelined co-run", ref, floor, share, mode, hip_pipe, _stats(it_p.graphs[(mode, 0)][2]),
            rep.model.boot_probe)
+    return it_p
 
 
 @pytest.mark.parametrize("mode", [-1, 0, 1])
@@ -262,7 +300,7 @@ def test_three_step_window_runs_the_eager_learner_and_matches_float64():
         else:
             raise AssertionError("no window with episode ends at all 3 steps")
         assert player._cache.pre_all is not None and player._cache.fh_all is not None
-        snap = learner_f64.snapshot(player)
+        snap = _snapshot(player)
         ref, floor, share = _references(snap, mode)
         _check("pzr1024x3 eager", ref, floor, share, mode, _bucket_grads(player.model, opt.bucket), _stats(stats),
                player.model.boot_probe, player._cache.h_all[:, 1:].transpose(0, 1))
@@ -325,7 +363,7 @@ def _eager(player, opt, args, mode, label):
     cache = player._cache
     in_cache = cache is not None and getattr(cache, "boot", None) is not None
     boot_action = None if (in_cache or not player.model.tat) else player.model.boot_action
-    snap = learner_f64.snapshot(player, boot_action=boot_action, actions=acts)
+    snap = _snapshot(player, boot_action=boot_action, actions=acts)
     ref, floor, share = _references(snap, mode)
     h = cache.h_all[:, 1:].transpose(0, 1) if cache is not None else None
     _check(label, ref, floor, share, mode, _bucket_grads(player.model, opt.bucket), _stats(stats), player.model.boot_probe, h)
