@@ -182,7 +182,7 @@ class Agent(object):
                                             and (obs0.numel() * obs0.element_size()) % 4 == 0)))
         if want_cache:
             # will every step's env.step run inside the policy step's last launch? (action_rollout asks the same question per
-            # step; envs that decline — RPF targets, 'Full' observations, --rescale, stacked frames, --occlusion, --fov, --footprints, NumpyVecEnv — step on
+            # step; envs that decline — RPF targets, 'Full' observations, --rescale, stacked frames, --occlusion, --fov, --footprints, --egocentric, NumpyVecEnv — step on
             # their own, and the cache must then not take the form whose hidden rows only k_act_step writes)
             env_fused = (self._buf is not None and hasattr(self.env, "fused_step_out") and num_steps >= 1
                          and self.env.fused_step_out((self._buf[0][1], self._buf[1][0], self._buf[2][0])) is not None)
@@ -281,7 +281,9 @@ class Agent(object):
     def _action_test_heuristic(self):
         """action_test with one or both players replaced by a heuristic player: the model's actions (where a model action can
         still reach the env — else the forward pass is skipped and the recurrent state stays as it is) with the replaced
-        columns overwritten by VecTrack2D.heuristic_actions for the state the step starts from."""
+        columns overwritten by VecTrack2D.heuristic_actions for the state the step starts from. The heuristic players plan in the
+        compass frame: where the env is egocentric for a replaced player, its moves go through VecEnv.relative_actions first, so
+        that step() turns them back into the moves the player chose."""
         tracker, target = self.heuristic
         if tracker not in (None, "pursuit") or target not in (None, "evade"):
             raise ValueError("Agent.heuristic = %r: the tracker's entry is None or 'pursuit', the target's None or 'evade'"
@@ -297,9 +299,10 @@ class Agent(object):
             self._heur_act = torch.zeros((self.num_envs, 2), dtype=torch.int64, device=self.device)
         roles = tuple(r for r in (tracker, target) if r is not None)
         core.heuristic_actions(roles, out=self._heur_act, dist=False)
-        step_actions = [self._heur_act[:, 0].contiguous() if tracker is not None else actions[0]]
+        relative = getattr(self.env, "relative_actions", lambda a, player: a)      # (--egocentric; else the moves as they are)
+        step_actions = [relative(self._heur_act[:, 0].contiguous(), 0) if tracker is not None else actions[0]]
         if target is not None:
-            step_actions.append(self._heur_act[:, 1].contiguous())
+            step_actions.append(relative(self._heur_act[:, 1].contiguous(), 1))
         elif actions is not None and len(actions) > 1:
             step_actions.append(actions[1])
         state_multi, self.reward, done, self.info = self.env.step(step_actions)

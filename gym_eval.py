@@ -82,6 +82,12 @@ parser.add_argument('--footprints', type=int, default=None, choices=tuple(range(
 parser.add_argument('--footprints-for', default=None, choices=('tracker', 'target', 'both'), metavar='WHO',
                     help='--footprints: whose window shows the other\'s prints: tracker, target or both (default: tracker; a '
                          'scripted Ram / Nav / RPF target reads no window: tracker only)')
+parser.add_argument('--egocentric', nargs='?', const=True, default=None, choices=('tracker', 'target', 'both'), metavar='WHO',
+                    help='egocentric view: a player\'s 13 x 13 window is turned so that the player always looks up (it faces the way '
+                         'of its last move; a new episode starts north-up), and its four actions mean forward / back / left / right. '
+                         'WHO: tracker, target or both; the bare flag means every model-driven player (the tracker alone where the '
+                         'target is scripted). --graphed-eval falls back to the eager evaluator; the heuristic players\' compass '
+                         'moves are translated. Not with --render')
 
 if __name__ == '__main__':
     args = parser.parse_args()
@@ -100,6 +106,12 @@ if __name__ == '__main__':
             and registry.spec(args.env)["target_mode"] in ("Ram", "Nav", "RPF")):
         parser.error("--footprints-for %s: the scripted target of %s reads no window, only the tracker's is painted there: use "
                      "--footprints-for tracker, or an id whose target is a player" % (args.footprints_for, args.env))
+    if args.egocentric is not None and args.render:
+        parser.error("--egocentric cannot be combined with --render: the renderer draws the tracker's window north-up")
+    if (args.egocentric in ("target", "both") and '2D' in args.env
+            and registry.spec(args.env)["target_mode"] in ("Ram", "Nav", "RPF")):
+        parser.error("--egocentric %s: the scripted target of %s reads no window and takes no action of a player: use "
+                     "--egocentric tracker, or an id whose target is a player" % (args.egocentric, args.env))
     build.build()
     check_path(args.log_dir)
     name = '{}_mon_log'.format(args.env)

@@ -153,6 +153,13 @@ parser.add_argument('--footprints', type=int, default=None, choices=tuple(range(
 parser.add_argument('--footprints-for', default=None, choices=('tracker', 'target', 'both'), metavar='WHO',
                     help='--footprints: whose window shows the other\'s prints: tracker, target or both (default: tracker; a '
                          'scripted Ram / Nav / RPF target reads no window: tracker only)')
+parser.add_argument('--egocentric', nargs='?', const=True, default=None, choices=('tracker', 'target', 'both'), metavar='WHO',
+                    help='egocentric view: a player\'s 13 x 13 window is turned so that the player always looks up (it faces the way '
+                         'of its last move; a new episode starts north-up), and its four actions mean forward / back / left / right. '
+                         'WHO: tracker, target or both; the bare flag means every model-driven player (the tracker alone where the '
+                         'target is scripted). In training and in the evaluation rounds (one launch ahead of the env step and one '
+                         'behind it, after --occlusion\'s, --fov\'s and --footprints\' where they are given, and the env step runs '
+                         'outside the policy step\'s last launch). Not with --tracking-stats, --sight-stats or --render')
 parser.add_argument('--map-bank', default=None, metavar='FILE',
                     help='train on the maps of a bank file (.npz / .txt: python -m active_tracking_rl_amd.map_bank) instead of '
                          'generated ones: every episode of every env, the in-launch auto-reset included, takes its map from the bank')
@@ -219,6 +226,18 @@ if __name__ == '__main__':
                 parser.error("--footprints-for %s: the scripted target of %s %s reads no window, only the tracker's is painted "
                              "there (the evaluation rounds run on --env-base): use --footprints-for tracker, or ids whose target "
                              "is a player" % (args.footprints_for, flag, env_id))
+    if args.egocentric is not None and (args.tracking_stats or args.sight_stats):
+        parser.error("--egocentric cannot be combined with --tracking-stats / --sight-stats: their action tables and offset maps "
+                     "are compass-framed")
+    if args.egocentric is not None and args.render:
+        parser.error("--egocentric cannot be combined with --render: the renderer draws the tracker's window north-up")
+    if args.egocentric in ("target", "both"):
+        from active_tracking_rl_amd import registry
+        for flag, env_id in (("--env", args.env), ("--env-base", args.env_base)):
+            if '2D' in env_id and registry.spec(env_id)["target_mode"] in ("Ram", "Nav", "RPF"):
+                parser.error("--egocentric %s: the scripted target of %s %s reads no window and takes no action of a player (the "
+                             "evaluation rounds run on --env-base): use --egocentric tracker, or ids whose target is a player"
+                             % (args.egocentric, flag, env_id))
     if args.map_priority is not None and args.map_bank is None:
         parser.error("--map-priority needs --map-bank: the priorities are over the maps of a bank")
     if args.map_priority is not None and (args.save_shard_state or args.load_shard_state is not None):
