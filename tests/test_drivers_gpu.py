@@ -427,8 +427,9 @@ def test_folded_tracker_action_embedding_gives_the_gradient_of_the_explicit_one(
     target's dW_ih product nor gathers dL/df by action for the embedding's gradient (two passes over [T N, 256] tensors each):
     the BPTT launch also leaves the column sums of dG by the row's tracker action, S [4, 512], and atr_embed_fold makes
     dW_ih += S^T E and d fc_action_tracker = S W_ih from them. Same rollout, fold on / off: every other gradient bit-identical,
-    the target's weight_ih and fc_action_tracker equal to summation-order round-off (checked against a float64 evaluation of
-    the same expressions from the explicit path's own dG is not needed: the explicit path IS the previous round's tested one).
+    the target's weight_ih and fc_action_tracker equal to summation-order round-off. This is fold against explicit through a whole
+    learner, at row counts that are multiples of 16; the float64 check of the BPTT launch's by-action sums, of atr_embed_fold and
+    of the folded node at small and ragged shapes is tests/test_lstm_bptt_f64_gpu.py.
     (1024 envs x 3 steps = 3072 rows: below the grouped weight-gradient launch's threshold — the fold then follows the product on
     the spot instead of as the group's post-flush hook.)"""
     from active_tracking_rl_amd import fused
