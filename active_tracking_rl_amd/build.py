@@ -15,8 +15,10 @@ LIB = os.path.join(HERE, "libtrack2d_hip.so")
 SOURCES = ["track2d_hip.hip", "stem_hip.hip", "policy_hip.hip", "lstm_hip.hip", "heads_hip.hip", "gemm_tn_hip.hip",
            "actor_step_hip.hip", "pair_gemm_hip.hip", "bptt_hip.hip", "driver_hip.hip", "gate_cell_hip.hip", "episode_stats_hip.hip",
            "gru_hip.hip", "render_hip.hip", "tracking_stats_hip.hip", "state_hip.hip", "stem_full_hip.hip", "heuristic_hip.hip",
-           "sight_stats_hip.hip", "occlusion_hip.hip", "fov_hip.hip", "footprints_hip.hip", "ego_hip.hip", "np_mode.cpp", "lt_gemm.cpp"]
-HEADERS = ["t2d_device.h", "t2d_rooms_rule.h", "atr_fov_rule.h", "atr_footprint_rule.h", "atr_ego_rule.h", os.path.join("..", "..", "include", "track2d.h"),
+           "sight_stats_hip.hip", "occlusion_hip.hip", "fov_hip.hip", "footprints_hip.hip", "ego_hip.hip", "memory_hip.hip",
+           "np_mode.cpp", "lt_gemm.cpp"]
+HEADERS = ["t2d_device.h", "t2d_rooms_rule.h", "atr_fov_rule.h", "atr_footprint_rule.h", "atr_ego_rule.h", "atr_memory_rule.h",
+           os.path.join("..", "..", "include", "track2d.h"),
            os.path.join("..", "..", "include", "atr_policy.h"), "atr_sample.h", "atr_cell.h",
            os.path.join("..", "..", "include", "track2d_np.h"), os.path.join("..", "..", "include", "atr_eval.h"),
            os.path.join("..", "..", "include", "atr_stats.h"), os.path.join("..", "..", "include", "atr_gru.h"),
@@ -27,7 +29,8 @@ HEADERS = ["t2d_device.h", "t2d_rooms_rule.h", "atr_fov_rule.h", "atr_footprint_
            os.path.join("..", "..", "include", "atr_stem_full.h"), os.path.join("..", "..", "include", "track2d_heuristic.h"),
            os.path.join("..", "..", "include", "atr_sight.h"), os.path.join("..", "..", "include", "atr_occlusion.h"),
            os.path.join("..", "..", "include", "track2d_bank.h"), os.path.join("..", "..", "include", "track2d_bank_prio.h"), os.path.join("..", "..", "include", "atr_fov.h"),
-           os.path.join("..", "..", "include", "atr_footprints.h"), os.path.join("..", "..", "include", "atr_ego.h")]
+           os.path.join("..", "..", "include", "atr_footprints.h"), os.path.join("..", "..", "include", "atr_ego.h"),
+           os.path.join("..", "..", "include", "atr_memory.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wno-unused-result"]
 LDFLAGS = ["--offload-arch=gfx950", "-fPIC", "-shared", "-ldl"]
@@ -57,6 +60,9 @@ NO_SCRATCH_FOV = {"fov_hip.hip": "k_fov"}
 NO_SCRATCH_FOOTPRINTS = {"footprints_hip.hip": "k_footprints"}
 # ... and the egocentric view (k_ego_actions, k_ego<uint8_t>, k_ego<float>: three cells per lane, parked in LDS)
 NO_SCRATCH_EGO = {"ego_hip.hip": "k_ego"}
+# ... and the map memory (k_memory<uint8_t>, k_memory<float>: three cells, four seen words and the 169-bit visible mask per lane; the
+# tiles the paint reads are staged in LDS)
+NO_SCRATCH_MEMORY = {"memory_hip.hip": "k_memory"}
 REMARKS = "-Rpass-analysis=kernel-resource-usage"
 
 
@@ -113,7 +119,7 @@ def build(force=False, verbose=False):
         part = NO_SCRATCH.get(src) or NO_SCRATCH_LEARNER.get(src) or NO_SCRATCH_RENDER.get(src) or NO_SCRATCH_STATS.get(src)
         part = part or NO_SCRATCH_STATE.get(src) or NO_SCRATCH_STEM_FULL.get(src) or NO_SCRATCH_HEURISTIC.get(src)
         part = part or NO_SCRATCH_SIGHT.get(src) or NO_SCRATCH_OCCLUSION.get(src) or NO_SCRATCH_FOV.get(src)
-        part = part or NO_SCRATCH_FOOTPRINTS.get(src) or NO_SCRATCH_EGO.get(src)
+        part = part or NO_SCRATCH_FOOTPRINTS.get(src) or NO_SCRATCH_EGO.get(src) or NO_SCRATCH_MEMORY.get(src)
         if part is None:
             subprocess.check_call(cmd)
             return

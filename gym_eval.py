@@ -88,6 +88,12 @@ parser.add_argument('--egocentric', nargs='?', const=True, default=None, choices
                          'WHO: tracker, target or both; the bare flag means every model-driven player (the tracker alone where the '
                          'target is scripted). --graphed-eval falls back to the eager evaluator; the heuristic players\' compass '
                          'moves are translated. Not with --render')
+parser.add_argument('--map-memory', nargs='?', const=True, default=None, choices=('tracker', 'target', 'both'), metavar='WHO',
+                    help='map memory: a cell of a player\'s 13 x 13 window that reads 5 ("unseen") shows 7 where the map has a wall '
+                         'and 8 where it has none, if the player has seen that cell in this episode; a new episode starts with an '
+                         'empty memory. Needs --occlusion or --fov. WHO: tracker, target or both; the bare flag means every '
+                         'model-driven player (the tracker alone where the target is scripted). --graphed-eval falls back to the eager '
+                         'evaluator. Not with --render')
 
 if __name__ == '__main__':
     args = parser.parse_args()
@@ -112,6 +118,18 @@ if __name__ == '__main__':
             and registry.spec(args.env)["target_mode"] in ("Ram", "Nav", "RPF")):
         parser.error("--egocentric %s: the scripted target of %s reads no window and takes no action of a player: use "
                      "--egocentric tracker, or an id whose target is a player" % (args.egocentric, args.env))
+    if args.map_memory is not None and not args.occlusion and args.fov is None:
+        parser.error("--map-memory needs --occlusion or --fov: without either no cell of a window ever reads 5, so there is nothing "
+                     "to fill in")
+    if args.map_memory is not None and args.render:
+        parser.error("--map-memory cannot be combined with --render: the drawn tracker's window comes from the renderer's own "
+                     "cells and would not show what is remembered")
+    if args.map_memory is not None and '2D' in args.env and registry.spec(args.env)["obs_type"] == "Full":
+        parser.error("--map-memory needs the 13 x 13 windows of a 'Partial' id, %s observes the whole map" % (args.env,))
+    if (args.map_memory in ("target", "both") and '2D' in args.env
+            and registry.spec(args.env)["target_mode"] in ("Ram", "Nav", "RPF")):
+        parser.error("--map-memory %s: the scripted target of %s reads no window, only the tracker can remember there: use "
+                     "--map-memory tracker, or an id whose target is a player" % (args.map_memory, args.env))
     build.build()
     check_path(args.log_dir)
     name = '{}_mon_log'.format(args.env)

@@ -160,6 +160,13 @@ parser.add_argument('--egocentric', nargs='?', const=True, default=None, choices
                          'target is scripted). In training and in the evaluation rounds (one launch ahead of the env step and one '
                          'behind it, after --occlusion\'s, --fov\'s and --footprints\' where they are given, and the env step runs '
                          'outside the policy step\'s last launch). Not with --tracking-stats, --sight-stats or --render')
+parser.add_argument('--map-memory', nargs='?', const=True, default=None, choices=('tracker', 'target', 'both'), metavar='WHO',
+                    help='map memory: a cell of a player\'s 13 x 13 window that reads 5 ("unseen") shows 7 where the map has a wall '
+                         'and 8 where it has none, if the player has seen that cell in this episode; a new episode starts with an '
+                         'empty memory. Needs --occlusion or --fov. WHO: tracker, target or both; the bare flag means every '
+                         'model-driven player (the tracker alone where the target is scripted). In training and in the evaluation rounds (one '
+                         'more launch per env step, after --occlusion\'s, --fov\'s and --footprints\' and ahead of --egocentric\'s turn, and '
+                         'the env step runs outside the policy step\'s last launch). Not with --tracking-stats, --sight-stats or --render')
 parser.add_argument('--map-bank', default=None, metavar='FILE',
                     help='train on the maps of a bank file (.npz / .txt: python -m active_tracking_rl_amd.map_bank) instead of '
                          'generated ones: every episode of every env, the in-launch auto-reset included, takes its map from the bank')
@@ -238,6 +245,26 @@ if __name__ == '__main__':
                 parser.error("--egocentric %s: the scripted target of %s %s reads no window and takes no action of a player (the "
                              "evaluation rounds run on --env-base): use --egocentric tracker, or ids whose target is a player"
                              % (args.egocentric, flag, env_id))
+    if args.map_memory is not None and not args.occlusion and args.fov is None:
+        parser.error("--map-memory needs --occlusion or --fov: without either no cell of a window ever reads 5, so there is nothing "
+                     "to fill in")
+    if args.map_memory is not None and (args.tracking_stats or args.sight_stats):
+        parser.error("--map-memory cannot be combined with --tracking-stats / --sight-stats: their bins were written for windows "
+                     "over {0, 1, 2, 4, 5}, and nobody has examined what a 7 or an 8 does to them")
+    if args.map_memory is not None and args.render:
+        parser.error("--map-memory cannot be combined with --render: the drawn tracker's window comes from the renderer's own "
+                     "cells and would not show what is remembered")
+    if args.map_memory is not None:
+        from active_tracking_rl_amd import registry
+        for flag, env_id in (("--env", args.env), ("--env-base", args.env_base)):
+            if '2D' in env_id and registry.spec(env_id)["obs_type"] == "Full":
+                parser.error("--map-memory needs the 13 x 13 windows of a 'Partial' id, %s %s observes the whole map (the "
+                             "evaluation rounds run on --env-base)" % (flag, env_id))
+            if (args.map_memory in ("target", "both") and '2D' in env_id
+                    and registry.spec(env_id)["target_mode"] in ("Ram", "Nav", "RPF")):
+                parser.error("--map-memory %s: the scripted target of %s %s reads no window, only the tracker can remember there "
+                             "(the evaluation rounds run on --env-base): use --map-memory tracker, or ids whose target is a player"
+                             % (args.map_memory, flag, env_id))
     if args.map_priority is not None and args.map_bank is None:
         parser.error("--map-priority needs --map-bank: the priorities are over the maps of a bank")
     if args.map_priority is not None and (args.save_shard_state or args.load_shard_state is not None):
