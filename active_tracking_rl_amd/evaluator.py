@@ -107,7 +107,7 @@ def account(rew, done, rsum=None, length=None, alive=None):
 
 def supported(env, model):
     """True exactly when the rollout's fused env step would be taken for this env and model: the env offers fused_step_out
-    (not for RPF targets, 'Full' observations, --rescale, stacked frames, --occlusion, --fov, --footprints, --map-memory, --egocentric, NumpyVecEnv), both players are present, R = 128 and the
+    (not for RPF targets, 'Full' observations, --rescale, stacked frames, --occlusion, --fov, --footprints, --map-memory, --noise-*, --egocentric, NumpyVecEnv), both players are present, R = 128 and the
     model's switches lead every step of a cached rollout to fused.act_env_step."""
     if not hasattr(env, "fused_step_out") or not hasattr(env, "rollout_buffers") or not hasattr(model, "new_cache"):
         return False

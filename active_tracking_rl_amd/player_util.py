@@ -182,7 +182,7 @@ class Agent(object):
                                             and (obs0.numel() * obs0.element_size()) % 4 == 0)))
         if want_cache:
             # will every step's env.step run inside the policy step's last launch? (action_rollout asks the same question per
-            # step; envs that decline — RPF targets, 'Full' observations, --rescale, stacked frames, --occlusion, --fov, --footprints, --map-memory, --egocentric, NumpyVecEnv — step on
+            # step; envs that decline — RPF targets, 'Full' observations, --rescale, stacked frames, --occlusion, --fov, --footprints, --map-memory, --noise-*, --egocentric, NumpyVecEnv — step on
             # their own, and the cache must then not take the form whose hidden rows only k_act_step writes)
             env_fused = (self._buf is not None and hasattr(self.env, "fused_step_out") and num_steps >= 1
                          and self.env.fused_step_out((self._buf[0][1], self._buf[1][0], self._buf[2][0])) is not None)
@@ -368,7 +368,7 @@ class Agent(object):
         sampler = getattr(self.model, "_sampler", None)
         if sampler is not None:
             d["sampler_counter"], d["sampler_seed"] = sampler.counter.cpu().clone(), int(sampler.seed)
-        for key in ("_frames", "_inv_flags", "_inv_fresh", "_facing", "_trail", "_seen"):
+        for key in ("_frames", "_inv_flags", "_inv_fresh", "_facing", "_trail", "_seen", "_noise_clock"):
             t = getattr(self.env, key, None)
             if t is not None:
                 d["env" + key] = t.cpu().clone()
@@ -412,6 +412,11 @@ class Agent(object):
                 raise ValueError("load_shard_state: the saved seen tiles have shape %s, this env's %s"
                                  % (tuple(d["env_seen"].shape), tuple(self.env._seen.shape)))
             self.env._seen.copy_(d["env_seen"].to(self.device))
+        if "env_noise_clock" in d and getattr(self.env, "_noise_clock", None) is not None:   # (--noise-*: in place, likewise)
+            if tuple(d["env_noise_clock"].shape) != tuple(self.env._noise_clock.shape):
+                raise ValueError("load_shard_state: the saved noise clock has shape %s, this env's %s"
+                                 % (tuple(d["env_noise_clock"].shape), tuple(self.env._noise_clock.shape)))
+            self.env._noise_clock.copy_(d["env_noise_clock"].to(self.device))
         self.state = self.env.observe()
 
     def clear_actions(self):

@@ -37,7 +37,8 @@ def default_args(**over):
              shared_optimizer=True, split=False, train_mode=-1, stack_frames=1, input_size=80, rnn_out=128,
              sleep_time=0, max_step=150000, init_step=-1, adv_step=None, num_envs=4096, max_grad_norm=None, obs_u8=True,
              full_stem=False, occlusion=False, fov=None, fov_target=None, fov_near=1, footprints=None,
-             footprints_for="tracker", egocentric=None, map_memory=None)
+             footprints_for="tracker", egocentric=None, map_memory=None, noise_flicker=None, noise_miss=None,
+             noise_ghost=None, noise_for=None)
     d.update(over)
     return argparse.Namespace(**d)
 

@@ -19,6 +19,17 @@ from active_tracking_rl_amd.test import evaluate, per_map_summary
 from active_tracking_rl_amd import registry
 from active_tracking_rl_amd.utils import check_path, setup_logger
 
+def _noise_rate(text):
+    """A sensor-noise rate: a float in [0, 1]."""
+    try:
+        p = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError("%r is not a number" % (text,))
+    if not 0.0 <= p <= 1.0:
+        raise argparse.ArgumentTypeError("%r is not a rate in [0, 1]" % (text,))
+    return p
+
+
 parser = argparse.ArgumentParser(description='A3C_EVAL')
 parser.add_argument('--env', default='Track2D-BlockPartialNav-v0', metavar='ENV', help='environment to evaluate on')
 parser.add_argument('--num-episodes', type=int, default=100, metavar='NE', help='how many episodes in evaluation')
@@ -94,6 +105,21 @@ parser.add_argument('--map-memory', nargs='?', const=True, default=None, choices
                          'empty memory. Needs --occlusion or --fov. WHO: tracker, target or both; the bare flag means every '
                          'model-driven player (the tracker alone where the target is scripted). --graphed-eval falls back to the eager '
                          'evaluator. Not with --render')
+parser.add_argument('--noise-flicker', type=_noise_rate, default=None, metavar='P',
+                    help='sensor noise: every free cell (0) and wall (1) of a noisy 13 x 13 window off its centre reads as the other '
+                         'of the two with probability P, drawn afresh at every env step. Any of --noise-flicker / --noise-miss / '
+                         '--noise-ghost turns the pass on. One more launch per env step ('
+                         'after --occlusion\'s, --fov\'s, --footprints\' and --map-memory\'s and ahead of --egocentric\'s turn); --graphed-eval '
+                         'falls back to the eager evaluator. Not with --render')
+parser.add_argument('--noise-miss', type=_noise_rate, default=None, metavar='P',
+                    help='sensor noise: with probability P per window and env step the other player is missing from a noisy window '
+                         '(its cell reads 0)')
+parser.add_argument('--noise-ghost', type=_noise_rate, default=None, metavar='P',
+                    help='sensor noise: with probability P per window and env step one cell of a noisy window, drawn uniformly, '
+                         'shows the other player if it read 0 (a false detection; never on a cell the player cannot see)')
+parser.add_argument('--noise-for', default=None, choices=('tracker', 'target', 'both'), metavar='WHO',
+                    help='sensor noise: whose window is noisy: tracker, target or both (default: every model-driven player, the '
+                         'tracker alone where the target is scripted)')
 
 if __name__ == '__main__':
     args = parser.parse_args()
@@ -130,6 +156,21 @@ if __name__ == '__main__':
             and registry.spec(args.env)["target_mode"] in ("Ram", "Nav", "RPF")):
         parser.error("--map-memory %s: the scripted target of %s reads no window, only the tracker can remember there: use "
                      "--map-memory tracker, or an id whose target is a player" % (args.map_memory, args.env))
+    noise_on = any(r is not None for r in (args.noise_flicker, args.noise_miss, args.noise_ghost))
+    if args.noise_for is not None and not noise_on:
+        parser.error("--noise-for needs --noise-flicker, --noise-miss or --noise-ghost")
+    if noise_on and not any((args.noise_flicker, args.noise_miss, args.noise_ghost)):
+        parser.error("--noise-flicker / --noise-miss / --noise-ghost: every rate is 0, so the pass would change nothing")
+    if noise_on and args.render:
+        parser.error("--noise-flicker / --noise-miss / --noise-ghost cannot be combined with --render: the drawn tracker's window "
+                     "comes from the renderer's own cells and would not show the noise")
+    if noise_on and '2D' in args.env and registry.spec(args.env)["obs_type"] == "Full":
+        parser.error("--noise-flicker / --noise-miss / --noise-ghost need the 13 x 13 windows of a 'Partial' id, %s observes the "
+                     "whole map" % (args.env,))
+    if (noise_on and args.noise_for in ("target", "both") and '2D' in args.env
+            and registry.spec(args.env)["target_mode"] in ("Ram", "Nav", "RPF")):
+        parser.error("--noise-for %s: the scripted target of %s reads no window, only the tracker's can be noisy there: use "
+                     "--noise-for tracker, or an id whose target is a player" % (args.noise_for, args.env))
     build.build()
     check_path(args.log_dir)
     name = '{}_mon_log'.format(args.env)

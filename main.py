@@ -47,6 +47,17 @@ from active_tracking_rl_amd.train import (GraphedIteration, PipelinedIteration, 
                                           sync_train_modes)
 from active_tracking_rl_amd.utils import ScalarWriter, log_train_scalars
 
+def _noise_rate(text):
+    """A sensor-noise rate: a float in [0, 1]."""
+    try:
+        p = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError("%r is not a number" % (text,))
+    if not 0.0 <= p <= 1.0:
+        raise argparse.ArgumentTypeError("%r is not a rate in [0, 1]" % (text,))
+    return p
+
+
 parser = argparse.ArgumentParser(description='A3C (MI355X data-parallel)')
 parser.add_argument('--lr', type=float, default=0.001, metavar='LR', help='learning rate (2D: 0.001, 3D: 0.0001)')
 parser.add_argument('--gamma', type=float, default=0.9, metavar='G', help='discount factor for rewards (default: 0.9)')
@@ -167,6 +178,21 @@ parser.add_argument('--map-memory', nargs='?', const=True, default=None, choices
                          'model-driven player (the tracker alone where the target is scripted). In training and in the evaluation rounds (one '
                          'more launch per env step, after --occlusion\'s, --fov\'s and --footprints\' and ahead of --egocentric\'s turn, and '
                          'the env step runs outside the policy step\'s last launch). Not with --tracking-stats, --sight-stats or --render')
+parser.add_argument('--noise-flicker', type=_noise_rate, default=None, metavar='P',
+                    help='sensor noise: every free cell (0) and wall (1) of a noisy 13 x 13 window off its centre reads as the other '
+                         'of the two with probability P, drawn afresh at every env step. Any of --noise-flicker / --noise-miss / '
+                         '--noise-ghost turns the pass on. In training and in the evaluation rounds (one more launch per env step, '
+                         'after --occlusion\'s, --fov\'s, --footprints\' and --map-memory\'s and ahead of --egocentric\'s turn, and '
+                         'the env step runs outside the policy step\'s last launch). Not with --tracking-stats, --sight-stats or --render')
+parser.add_argument('--noise-miss', type=_noise_rate, default=None, metavar='P',
+                    help='sensor noise: with probability P per window and env step the other player is missing from a noisy window '
+                         '(its cell reads 0)')
+parser.add_argument('--noise-ghost', type=_noise_rate, default=None, metavar='P',
+                    help='sensor noise: with probability P per window and env step one cell of a noisy window, drawn uniformly, '
+                         'shows the other player if it read 0 (a false detection; never on a cell the player cannot see)')
+parser.add_argument('--noise-for', default=None, choices=('tracker', 'target', 'both'), metavar='WHO',
+                    help='sensor noise: whose window is noisy: tracker, target or both (default: every model-driven player, the '
+                         'tracker alone where the target is scripted)')
 parser.add_argument('--map-bank', default=None, metavar='FILE',
                     help='train on the maps of a bank file (.npz / .txt: python -m active_tracking_rl_amd.map_bank) instead of '
                          'generated ones: every episode of every env, the in-launch auto-reset included, takes its map from the bank')
@@ -265,6 +291,28 @@ if __name__ == '__main__':
                 parser.error("--map-memory %s: the scripted target of %s %s reads no window, only the tracker can remember there "
                              "(the evaluation rounds run on --env-base): use --map-memory tracker, or ids whose target is a player"
                              % (args.map_memory, flag, env_id))
+    noise_on = any(r is not None for r in (args.noise_flicker, args.noise_miss, args.noise_ghost))
+    if args.noise_for is not None and not noise_on:
+        parser.error("--noise-for needs --noise-flicker, --noise-miss or --noise-ghost")
+    if noise_on and not any((args.noise_flicker, args.noise_miss, args.noise_ghost)):
+        parser.error("--noise-flicker / --noise-miss / --noise-ghost: every rate is 0, so the pass would change nothing")
+    if noise_on and (args.tracking_stats or args.sight_stats):
+        parser.error("--noise-flicker / --noise-miss / --noise-ghost cannot be combined with --tracking-stats / --sight-stats: "
+                     "their bins assume exactly one true 4 / 2 in a window")
+    if noise_on and args.render:
+        parser.error("--noise-flicker / --noise-miss / --noise-ghost cannot be combined with --render: the drawn tracker's window "
+                     "comes from the renderer's own cells and would not show the noise")
+    if noise_on:
+        from active_tracking_rl_amd import registry
+        for flag, env_id in (("--env", args.env), ("--env-base", args.env_base)):
+            if '2D' in env_id and registry.spec(env_id)["obs_type"] == "Full":
+                parser.error("--noise-flicker / --noise-miss / --noise-ghost need the 13 x 13 windows of a 'Partial' id, %s %s "
+                             "observes the whole map (the evaluation rounds run on --env-base)" % (flag, env_id))
+            if (args.noise_for in ("target", "both") and '2D' in env_id
+                    and registry.spec(env_id)["target_mode"] in ("Ram", "Nav", "RPF")):
+                parser.error("--noise-for %s: the scripted target of %s %s reads no window, only the tracker's can be noisy there "
+                             "(the evaluation rounds run on --env-base): use --noise-for tracker, or ids whose target is a player"
+                             % (args.noise_for, flag, env_id))
     if args.map_priority is not None and args.map_bank is None:
         parser.error("--map-priority needs --map-bank: the priorities are over the maps of a bank")
     if args.map_priority is not None and (args.save_shard_state or args.load_shard_state is not None):
