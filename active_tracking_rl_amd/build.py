@@ -16,9 +16,9 @@ SOURCES = ["track2d_hip.hip", "stem_hip.hip", "policy_hip.hip", "lstm_hip.hip", 
            "actor_step_hip.hip", "pair_gemm_hip.hip", "bptt_hip.hip", "driver_hip.hip", "gate_cell_hip.hip", "episode_stats_hip.hip",
            "gru_hip.hip", "render_hip.hip", "tracking_stats_hip.hip", "state_hip.hip", "stem_full_hip.hip", "heuristic_hip.hip",
            "sight_stats_hip.hip", "occlusion_hip.hip", "fov_hip.hip", "footprints_hip.hip", "ego_hip.hip", "memory_hip.hip",
-           "noise_hip.hip", "np_mode.cpp", "lt_gemm.cpp"]
+           "noise_hip.hip", "view_hip.hip", "np_mode.cpp", "lt_gemm.cpp"]
 HEADERS = ["t2d_device.h", "t2d_rooms_rule.h", "atr_fov_rule.h", "atr_footprint_rule.h", "atr_ego_rule.h", "atr_memory_rule.h",
-           "atr_noise_rule.h",
+           "atr_noise_rule.h", "atr_view_rule.h",
            os.path.join("..", "..", "include", "track2d.h"),
            os.path.join("..", "..", "include", "atr_policy.h"), "atr_sample.h", "atr_cell.h",
            os.path.join("..", "..", "include", "track2d_np.h"), os.path.join("..", "..", "include", "atr_eval.h"),
@@ -31,7 +31,8 @@ HEADERS = ["t2d_device.h", "t2d_rooms_rule.h", "atr_fov_rule.h", "atr_footprint_
            os.path.join("..", "..", "include", "atr_sight.h"), os.path.join("..", "..", "include", "atr_occlusion.h"),
            os.path.join("..", "..", "include", "track2d_bank.h"), os.path.join("..", "..", "include", "track2d_bank_prio.h"), os.path.join("..", "..", "include", "atr_fov.h"),
            os.path.join("..", "..", "include", "atr_footprints.h"), os.path.join("..", "..", "include", "atr_ego.h"),
-           os.path.join("..", "..", "include", "atr_memory.h"), os.path.join("..", "..", "include", "atr_noise.h")]
+           os.path.join("..", "..", "include", "atr_memory.h"), os.path.join("..", "..", "include", "atr_noise.h"),
+           os.path.join("..", "..", "include", "atr_view.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wno-unused-result"]
 LDFLAGS = ["--offload-arch=gfx950", "-fPIC", "-shared", "-ldl"]
@@ -66,6 +67,9 @@ NO_SCRATCH_EGO = {"ego_hip.hip": "k_ego"}
 NO_SCRATCH_MEMORY = {"memory_hip.hip": "k_memory"}
 # ... and the sensor noise (k_noise<uint8_t>, k_noise<float>: three cells and two Philox blocks per lane)
 NO_SCRATCH_NOISE = {"noise_hip.hip": "k_noise"}
+# ... and the player views (k_view_cells, k_view_rgb, each for uint8_t and float windows: the tile, the windows' codes and a band's
+# colours are staged in LDS)
+NO_SCRATCH_VIEW = {"view_hip.hip": "k_view"}
 REMARKS = "-Rpass-analysis=kernel-resource-usage"
 
 
@@ -123,7 +127,7 @@ def build(force=False, verbose=False):
         part = part or NO_SCRATCH_STATE.get(src) or NO_SCRATCH_STEM_FULL.get(src) or NO_SCRATCH_HEURISTIC.get(src)
         part = part or NO_SCRATCH_SIGHT.get(src) or NO_SCRATCH_OCCLUSION.get(src) or NO_SCRATCH_FOV.get(src)
         part = part or NO_SCRATCH_FOOTPRINTS.get(src) or NO_SCRATCH_EGO.get(src) or NO_SCRATCH_MEMORY.get(src)
-        part = part or NO_SCRATCH_NOISE.get(src)
+        part = part or NO_SCRATCH_NOISE.get(src) or NO_SCRATCH_VIEW.get(src)
         if part is None:
             subprocess.check_call(cmd)
             return

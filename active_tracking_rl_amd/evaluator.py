@@ -158,7 +158,8 @@ class GreedyEvaluator(_GraphedSchedule):
 
     def _make_env(self):
         return create_env(self.env_id, eval_args(self.args), num_envs=max(2, self.episodes), device=str(self.device),
-                          env_id_base=getattr(self.args, "eval_env_id_base", 1 << 20), obs_u8=True)
+                          env_id_base=getattr(self.args, "eval_env_id_base", 1 << 20), obs_u8=True,
+                          views=False)              # (--view draws the eager round: test.evaluate)
 
     def _player(self, env, accounts):
         p = Agent(self.model, env, self.args, None, self.device)

@@ -40,15 +40,34 @@ class FrameWriter(object):
     def frame(self, t, done=None):
         if self.k == 0 or not self.open.any():
             return
-        frames = self.core.render_rgb(self.ids, scale=self.scale).cpu().numpy()
+        frames = self.draw().cpu().numpy()
         fin = np.zeros(self.k, bool) if done is None else (done[:self.k].cpu().numpy() != 0)
         for e in np.nonzero(self.open)[0]:
             write_png(os.path.join(self.dir, "ep%03d" % e, "step%04d.png" % t), frames[e])
         self.open &= ~fin
 
+    def draw(self):
+        return self.core.render_rgb(self.ids, scale=self.scale)
+
     def close(self):
         tr = self.core.traces(0, self.episodes)
         np.savez_compressed(os.path.join(self.dir, "traces.npz"), pos=tr["pos"], len=tr["len"])
+
+
+class ViewWriter(FrameWriter):
+    """--view: FrameWriter's file tree with the frames of atr_view_rgb (VecEnv.view_rgb, ONE launch per step): the map as
+    `viewer` was shown it and both players' windows as they were handed to the policy. There is no trace store, so close()
+    writes nothing."""
+
+    def __init__(self, ev, directory, eps, scale, episodes, viewer=0):
+        FrameWriter.__init__(self, ev, directory, eps, scale, episodes)
+        self.ev, self.viewer = ev, viewer
+
+    def draw(self):
+        return self.ev.view_rgb(self.ids, scale=self.scale, viewer=self.viewer)
+
+    def close(self):
+        pass
 
 
 _warned_heuristic_graphed = False
@@ -75,7 +94,7 @@ def heuristic_players(model, env_id, heuristic_tracker=None, heuristic_target=No
 
 @torch.no_grad()
 def evaluate(model, env_id, args, device, episodes, seed=None, graphed=False, render_dir=None, heuristic_tracker=None,
-             heuristic_target=None, info=None):
+             heuristic_target=None, info=None, view_dir=None):
     """Run `episodes` envs of `env_id` in parallel until each has finished ONE episode. Returns per-episode reward
     sums [episodes, 2] and lengths [episodes] (numpy). graphed: the round on the rollout's kernels as replayed hipGraphs
     (evaluator.GreedyEvaluator) where they apply, else — with one warning line — the eager round below.
@@ -85,6 +104,9 @@ def evaluate(model, env_id, args, device, episodes, seed=None, graphed=False, re
     the step kernels treat it like any other env — while its trace stays closed: no masked reset is needed.)
     heuristic_tracker='pursuit' / heuristic_target='evade': that player's actions come from the heuristic player
     (heuristic_players: the round is the eager one; model may be None when no model action reaches the env).
+    view_dir: draw the first args.view_eps episodes into it as the players were shown them (ViewWriter; args.view names the
+    viewer). Like a rendered round it runs here, on a shard without the in-launch auto-reset, so that a terminal frame shows the
+    terminal state; there is no traces.npz. Not together with render_dir.
     info: a dict that receives what the round knows beyond its return value — with --eval-map-bank, info['map_index']: int32
     [episodes], the bank index of each evaluation episode's map (map_index() right after the reset)."""
     global _warned_heuristic_graphed
@@ -95,8 +117,13 @@ def evaluate(model, env_id, args, device, episodes, seed=None, graphed=False, re
                                                 "actions from the model")
             _warned_heuristic_graphed = True
         graphed = False
+    if render_dir is not None and view_dir is not None:
+        raise ValueError("evaluate: render_dir and view_dir are one drawing mode each, give one")
     if graphed and render_dir is not None:
         logging.getLogger(__name__).warning("--render uses the eager evaluation round: the graphed step restarts episodes in-launch")
+        graphed = False
+    if graphed and view_dir is not None:
+        logging.getLogger(__name__).warning("--view uses the eager evaluation round: the graphed step restarts episodes in-launch")
         graphed = False
     if graphed:
         from . import evaluator
@@ -109,7 +136,8 @@ def evaluate(model, env_id, args, device, episodes, seed=None, graphed=False, re
         except evaluator.Unsupported as ex:
             logging.getLogger(__name__).warning("graphed evaluation falls back to the eager round: %s", ex)
     ev = create_env(env_id, eval_args(args), num_envs=max(2, episodes), device=str(device),
-                    env_id_base=getattr(args, "eval_env_id_base", 1 << 20), traces=render_dir is not None)
+                    env_id_base=getattr(args, "eval_env_id_base", 1 << 20), traces=render_dir is not None,
+                    views=view_dir is not None, auto_reset=False if view_dir is not None else None)
     n = ev.num_envs
     was_training = model is not None and model.training
     if model is not None:
@@ -125,6 +153,10 @@ def evaluate(model, env_id, args, device, episodes, seed=None, graphed=False, re
     frames = None
     if render_dir is not None:
         frames = FrameWriter(ev, render_dir, getattr(args, "render_eps", 4), getattr(args, "render_scale", 4), episodes)
+        frames.frame(0)
+    elif view_dir is not None:
+        frames = ViewWriter(ev, view_dir, getattr(args, "view_eps", 4), getattr(args, "view_scale", 4), episodes,
+                            getattr(args, "view", None) or "tracker")
         frames.frame(0)
     for t in range(ev.core_max_steps()):
         player.action_test()
@@ -259,9 +291,13 @@ def test(args, shared_model, train_modes, n_iters, rounds=None, state=None):
         t0 = time.time()
         n_iter = int(sum(n_iters))
         render_dir = os.path.join(args.log_dir, 'render', 'iter{0}'.format(n_iter)) if getattr(args, "render", False) else None
+        view_dir = None
+        if getattr(args, "view", None):
+            view_dir = os.path.join(getattr(args, "view_dir", None) or os.path.join(args.log_dir, 'view'), 'iter{0}'.format(n_iter))
         info = {}
         rsum, length = evaluate(shared_model, env_id, args, device, args.test_eps,
-                                graphed=bool(getattr(args, "graphed_eval", False)), render_dir=render_dir, info=info)
+                                graphed=bool(getattr(args, "graphed_eval", False)), render_dir=render_dir, info=info,
+                                view_dir=view_dir)
         schedule_train_modes(args, train_modes, n_iter, state)                       # test.py:84-92
         # test.py:93-97: one record per evaluation episode at step n_iter. test/fps in the reference is the env steps per
         # second of the evaluator's one env; here the episodes of a round run as one batch, so it is the round's env steps

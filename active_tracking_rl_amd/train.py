@@ -38,7 +38,7 @@ def default_args(**over):
              sleep_time=0, max_step=150000, init_step=-1, adv_step=None, num_envs=4096, max_grad_norm=None, obs_u8=True,
              full_stem=False, occlusion=False, fov=None, fov_target=None, fov_near=1, footprints=None,
              footprints_for="tracker", egocentric=None, map_memory=None, noise_flicker=None, noise_miss=None,
-             noise_ghost=None, noise_for=None)
+             noise_ghost=None, noise_for=None, view=None, view_dir=None, view_eps=4, view_scale=4)
     d.update(over)
     return argparse.Namespace(**d)
 
@@ -62,7 +62,7 @@ def make_player(args, device, rank=0, world_size=1, env=None, model=None, optimi
     torch.manual_seed(args.seed)          # same init on every rank (replicas must start identical)
     if env is None:
         env = create_env(args.env, args, num_envs=args.num_envs, device=str(device),
-                         env_id_base=rank * args.num_envs, traces=False)    # (--render draws the evaluation rounds)
+                         env_id_base=rank * args.num_envs, traces=False, views=False)    # (--render / --view draw the evaluation rounds)
     if model is None:
         model = build_model(env.observation_space, env.action_space, args, device).to(device)
     model.train()

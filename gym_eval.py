@@ -45,6 +45,16 @@ parser.add_argument('--render-dir', default=None, metavar='DIR',
                     help='--render: folder for ep{e:03d}/step{t:04d}.png and traces.npz (default: <log-dir>/render)')
 parser.add_argument('--render-eps', type=int, default=4, metavar='K', help='--render: episodes to draw (default: 4)')
 parser.add_argument('--render-scale', type=int, default=4, metavar='S', help='--render: pixels per map cell, 1..8 (default: 4)')
+parser.add_argument('--view', nargs='?', const='tracker', default=None, choices=('tracker', 'target'), metavar='WHO',
+                    help='draw what each player was shown: the first --view-eps episodes as PNG frames under --view-dir, each the '
+                         'map as WHO (tracker or target; the bare flag means tracker) was shown it — what it was told where it saw '
+                         'something, the dimmed truth where it saw nothing — next to both players\' 13 x 13 windows as they were '
+                         'handed to the policy. Combines with every observation flag (--occlusion, --fov, --footprints, '
+                         '--map-memory, --noise-*, --egocentric); runs the eager round. Not with --render')
+parser.add_argument('--view-dir', default=None, metavar='DIR',
+                    help='--view: folder for ep{e:03d}/step{t:04d}.png (default: <log-dir>/view)')
+parser.add_argument('--view-eps', type=int, default=4, metavar='K', help='--view: episodes to draw (default: 4)')
+parser.add_argument('--view-scale', type=int, default=4, metavar='S', help='--view: pixels per canvas cell, 1..8 (default: 4)')
 parser.add_argument('--heuristic-tracker', default=None, choices=('pursuit',),
                     help='pursuit: the tracker walks a shortest path to the target (computed on the device) instead of following '
                          'a checkpoint')
@@ -123,6 +133,10 @@ parser.add_argument('--noise-for', default=None, choices=('tracker', 'target', '
 
 if __name__ == '__main__':
     args = parser.parse_args()
+    if args.view is not None and args.render:
+        parser.error("--view cannot be combined with --render: one drawing mode per run")
+    if args.view is not None and '2D' in args.env and registry.spec(args.env)["obs_type"] == "Full":
+        parser.error("--view needs the 13 x 13 windows of a 'Partial' id, %s observes the whole map" % (args.env,))
     if args.fov is None and args.fov_target is not None:
         parser.error("--fov-target needs --fov")
     if args.fov is not None and args.render:
@@ -196,10 +210,12 @@ if __name__ == '__main__':
         model.player1.load_state_dict(load(args.load_target))             # :88-92
     args.gpu_ids = [device.index]
     render_dir = (args.render_dir or os.path.join(args.log_dir, 'render')) if args.render else None
+    view_dir = (args.view_dir or os.path.join(args.log_dir, 'view')) if args.view is not None else None
     args.eval_map_bank, args.map_bank = args.map_bank, None        # (the evaluation shard's flag: environment.eval_args)
     info = {}
     rsum, length = evaluate(model, args.env, args, device, args.num_episodes, graphed=args.graphed_eval, render_dir=render_dir,
-                            heuristic_tracker=args.heuristic_tracker, heuristic_target=args.heuristic_target, info=info)
+                            heuristic_tracker=args.heuristic_tracker, heuristic_target=args.heuristic_target, info=info,
+                            view_dir=view_dir)
     reward_mean, reward_std = rsum.mean(0), rsum.std(0)
     len_mean, len_std = length.mean(), length.std()
     success_rate = float((length >= 500).mean())

@@ -97,6 +97,14 @@ parser.add_argument('--rescale', dest='rescale', action='store_true', help='resc
 parser.add_argument('--render', dest='render', action='store_true',
                     help='draw the first --render-eps episodes of every test round on the device and write them as PNG frames '
                          'under <log-dir>/render/iter{n}/ (such rounds run eagerly on a shard that keeps episode traces)')
+parser.add_argument('--view', nargs='?', const='tracker', default=None, choices=('tracker', 'target'), metavar='WHO',
+                    help='draw what each player was shown: the first --view-eps episodes of every test round as PNG frames under '
+                         '<log-dir>/view/iter{n}/, each the map as WHO (tracker or target; the bare flag means tracker) was shown '
+                         'it next to both players\' 13 x 13 windows as they were handed to the policy. Combines with every '
+                         'observation flag; such rounds run eagerly. The training envs are untouched. Not with --render')
+parser.add_argument('--view-dir', default=None, metavar='DIR', help='--view: the folder that holds iter{n}/ (default: <log-dir>/view)')
+parser.add_argument('--view-eps', type=int, default=4, metavar='K', help='--view: episodes to draw per test round (default: 4)')
+parser.add_argument('--view-scale', type=int, default=4, metavar='S', help='--view: pixels per canvas cell, 1..8 (default: 4)')
 parser.add_argument('--eval-heuristic', dest='eval_heuristic', action='store_true',
                     help='after every evaluation round, two more rounds of --test-eps episodes on --env against the heuristic '
                          'players: the tracker against the evading target (test/vs_evade/reward0, test/vs_evade/eps_len) and the '
@@ -235,6 +243,13 @@ if __name__ == '__main__':
                      "args.adv_step there without defining the flag and stops with an AttributeError at the first switch")
     if args.max_grad_norm is not None and args.max_grad_norm <= 0:
         parser.error("--max-grad-norm must be positive")
+    if args.view is not None and args.render:
+        parser.error("--view cannot be combined with --render: one drawing mode per run")
+    if args.view is not None:
+        from active_tracking_rl_amd import registry
+        view_id = args.env if args.env_base is None else args.env_base
+        if '2D' in view_id and registry.spec(view_id)["obs_type"] == "Full":
+            parser.error("--view needs the 13 x 13 windows of a 'Partial' id, the evaluated %s observes the whole map" % (view_id,))
     if args.fov is None and args.fov_target is not None:
         parser.error("--fov-target needs --fov")
     if args.fov is not None and (args.tracking_stats or args.sight_stats):
