@@ -136,14 +136,20 @@ __global__ __launch_bounds__(kHeadsBlock) void k_heads_loss(const HeadsLossMulti
         float p[NAx], se = 0.f;
 #pragma unroll
         for (int i = 0; i < NAx; i++) { p[i] = i < A ? expf(z[i] - mx) : 0.f; se += p[i]; }
-        const float lse = mx + logf(se);
-        float ent = 0.f, logp_a = 0.f;
+        const float lg = logf(se);
+        const float lse = mx + lg;
+        // ent_s, the entropy STATISTIC: log p = (z - max) - log(sum), in this order. z - lse rounds at the logits' magnitude (7.6e-6
+        // at |z| >= 128), which is all there is of log p = -1e-6 on the top action of a peaked row, where p log p is the row's whole
+        // entropy: the logged entropy of a trained policy missed the float64 rule by 2x (tests/test_cell_edges_gpu.py). The loss and
+        // its gradient, which that test holds as they are, keep ent: every trained number stays bit for bit what it was
+        float ent = 0.f, ent_s = 0.f, logp_a = 0.f;
 #pragma unroll
         for (int i = 0; i < NAx; i++) {
             if (i < A) {
                 p[i] = p[i] / se;
                 const float lp = z[i] - lse;
                 ent -= lp * p[i];
+                ent_s -= ((z[i] - mx) - lg) * p[i];
                 if (i == act) logp_a = lp;
             }
         }
@@ -180,7 +186,7 @@ __global__ __launch_bounds__(kHeadsBlock) void k_heads_loss(const HeadsLossMulti
         gbc += dv; gbx += dpred;
         s_pol += -logp_a * gae - a.w_ent * ent;
         s_val += 0.5f * (ret - v) * (ret - v);
-        s_ent += ent;
+        s_ent += ent_s;
         s_aux += aux_abs;
     }
     // block reduction over the row slots (fixed order), one record per workgroup
